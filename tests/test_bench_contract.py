@@ -60,6 +60,39 @@ def test_bench_torchrun_world2_aggregates():
 
 
 @pytest.mark.timeout(300)
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float .npy, and
+    two runs with the same arguments start from identical inputs (seeded init
+    and data), so on CPU their outputs agree. --full is accepted alongside."""
+    import numpy as np
+    # hide any GPU: the comparison below relies on CPU arithmetic
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", CUDA_VISIBLE_DEVICES="")
+    dumps = []
+    for tag, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / tag
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+             "--warmup", "1", "--batch", "4", "--model", "mnist_mlp",
+             "--dump-outputs", str(d)] + extra,
+            capture_output=True, text=True, cwd=REPO, env=env, timeout=240)
+        assert out.returncode == 0, out.stderr[-1500:]
+        r = _extract_json(out.stdout)
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert {"loss", "logits", "params"} <= set(a) and set(a) == set(b)
+    assert a["logits"].shape == (4, 10) and a["loss"].shape == (1,)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64)
+        assert np.isfinite(a[name]).all()
+        # fp32 CPU arithmetic on identical inputs; allow last-bit reduction
+        # order differences only
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-5, atol=1e-6,
+                                   err_msg=name)
+
+
+@pytest.mark.timeout(300)
 def test_bench_no_launcher_does_not_hang():
     """`--gpus 8` without torchrun must run single-process (no peer wait)."""
     out = subprocess.run(
