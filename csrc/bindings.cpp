@@ -8,7 +8,8 @@
 extern "C" {
 int tfosr_bn_fast_blocks(long, int, int, int);
 void tfosr_bn_stats(const void*, int, int, float*, int, int, int, long, hipStream_t);
-void tfosr_bn_finalize(const float*, int, float*, float*, float*, float*,
+void tfosr_bn_finalize(const float*, int, const void*, int, int, long,
+                       float*, float*, float*, float*,
                        long, int, float, float, hipStream_t);
 void tfosr_bn_apply(const void*, const void*, void*, unsigned char*,
                     const float*, const float*,
@@ -99,9 +100,40 @@ BNLayout bn_layout(const at::Tensor& x) {
 }
 
 int dtype_flag(const at::Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), "bn: input must be a GPU tensor");
   if (x.scalar_type() == at::kBFloat16) return 1;
   TORCH_CHECK(x.scalar_type() == at::kFloat, "expected float32 or bfloat16");
   return 0;
+}
+
+// The launchers take raw pointers: everything they index is checked here.
+
+// per-channel parameter / statistic: fp32, contiguous, length C, on x's device
+void bn_check_channel_vec(const at::Tensor& t, const at::Tensor& x, int C,
+                          const char* name) {
+  TORCH_CHECK(t.device() == x.device(), "bn: ", name, " must be on ", x.device(),
+              ", got ", t.device());
+  TORCH_CHECK(t.scalar_type() == at::kFloat, "bn: ", name, " must be float32");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == C, "bn: ", name,
+              " must have shape [", C, "]");
+  TORCH_CHECK(t.is_contiguous(), "bn: ", name, " must be contiguous");
+}
+
+// activation-shaped tensor: same sizes, dtype and device as x and, when
+// same_layout is set, the same memory layout
+void bn_check_like(const at::Tensor& t, const at::Tensor& x, bool nhwc,
+                   bool same_layout, const char* name) {
+  TORCH_CHECK(t.device() == x.device(), "bn: ", name, " must be on ", x.device(),
+              ", got ", t.device());
+  TORCH_CHECK(t.scalar_type() == x.scalar_type(), "bn: ", name,
+              " must have the input's dtype");
+  TORCH_CHECK(t.sizes() == x.sizes(), "bn: ", name,
+              " must have the input's shape");
+  if (same_layout) {
+    TORCH_CHECK(nhwc ? t.is_contiguous(at::MemoryFormat::ChannelsLast)
+                     : t.is_contiguous(),
+                "bn: ", name, " must have the input's memory layout");
+  }
 }
 
 std::vector<at::Tensor> bn_fwd_train(at::Tensor x, c10::optional<at::Tensor> res,
@@ -112,9 +144,13 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, c10::optional<at::Tensor> res
   int bf = dtype_flag(x);
   const void* res_ptr = nullptr;
   if (res.has_value()) {
-    TORCH_CHECK(res->sizes() == x.sizes() && res->scalar_type() == x.scalar_type());
+    bn_check_like(*res, x, l.nhwc, true, "res");
     res_ptr = res->data_ptr();
   }
+  bn_check_channel_vec(w, x, l.C, "weight");
+  bn_check_channel_vec(b, x, l.C, "bias");
+  bn_check_channel_vec(rm, x, l.C, "running_mean");
+  bn_check_channel_vec(rv, x, l.C, "running_var");
   auto opts = x.options().dtype(at::kFloat);
   long M = (long)l.N * l.HW;
   int nb = tfosr_bn_fast_blocks(M * l.C, l.C, bf, l.nhwc);
@@ -136,7 +172,7 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, c10::optional<at::Tensor> res
   auto s = cur_stream();
   tfosr_bn_stats(x.data_ptr(), bf, l.nhwc, ws.data_ptr<float>(), nb,
                  l.N, l.C, l.HW, s);
-  tfosr_bn_finalize(ws.data_ptr<float>(), nb,
+  tfosr_bn_finalize(ws.data_ptr<float>(), nb, x.data_ptr(), bf, l.nhwc, l.HW,
                     save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),
                     rm.data_ptr<float>(), rv.data_ptr<float>(), M, l.C,
                     (float)momentum, (float)eps, s);
@@ -152,7 +188,15 @@ at::Tensor bn_fwd_eval(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor w
                        bool relu) {
   auto l = bn_layout(x);
   int bf = dtype_flag(x);
-  const void* res_ptr = res.has_value() ? res->data_ptr() : nullptr;
+  const void* res_ptr = nullptr;
+  if (res.has_value()) {
+    bn_check_like(*res, x, l.nhwc, true, "res");
+    res_ptr = res->data_ptr();
+  }
+  bn_check_channel_vec(w, x, l.C, "weight");
+  bn_check_channel_vec(b, x, l.C, "bias");
+  bn_check_channel_vec(rm, x, l.C, "running_mean");
+  bn_check_channel_vec(rv, x, l.C, "running_var");
   auto rstd = at::rsqrt(rv + eps);
   auto y = at::empty_like(x);
   tfosr_bn_apply(x.data_ptr(), res_ptr, y.data_ptr(), nullptr,
@@ -169,6 +213,11 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y,
                                at::Tensor save_rstd, bool relu, bool grad_res) {
   auto l = bn_layout(x);
   int bf = dtype_flag(x);
+  bn_check_like(dy, x, l.nhwc, false, "dy");
+  bn_check_like(y, x, l.nhwc, true, "y");
+  bn_check_channel_vec(w, x, l.C, "weight");
+  bn_check_channel_vec(save_mean, x, l.C, "save_mean");
+  bn_check_channel_vec(save_rstd, x, l.C, "save_rstd");
   dy = l.nhwc ? dy.contiguous(at::MemoryFormat::ChannelsLast) : dy.contiguous();
   auto opts = x.options().dtype(at::kFloat);
   long total = (long)l.N * l.HW * l.C;
@@ -189,6 +238,12 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y,
       mask.numel() ? mask.data_ptr<unsigned char>() : nullptr;
   TORCH_CHECK(!(relu && nb > 0) || mask_ptr != nullptr,
               "fast-path relu backward requires the forward bitmask");
+  if (relu && nb > 0) {
+    TORCH_CHECK(mask.device() == x.device() && mask.scalar_type() == at::kByte &&
+                    mask.is_contiguous() && mask.numel() == total / (bf ? 8 : 4),
+                "bn: mask must be the contiguous uint8 bitmask bn_fwd_train "
+                "returned for this input");
+  }
   tfosr_bn_bwd_stats(x.data_ptr(), dy.data_ptr(), y.data_ptr(), mask_ptr,
                      gout_ptr,
                      save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),

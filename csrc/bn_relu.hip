@@ -8,9 +8,15 @@
 //  * all hot-loop index math in uint32 (64-bit div/mod is ~40 VALU cycles and
 //    made the first version 10x off roofline); launchers fall back to the
 //    generic kernels when a tensor exceeds 2^31 elements.
-//  * NHWC reductions: thread t owns the 8 fixed channels (t*8..t*8+7) mod C
-//    (valid when C | 2048 — every ResNet/UNet width), accumulating in
-//    registers over a grid-stride loop, one atomicAdd per channel at the end.
+//  * NHWC reductions: a thread owns the fixed channels of its first vector,
+//    (i*V .. i*V+V-1) mod C, accumulating in registers over a grid-stride
+//    loop, one LDS atomicAdd per channel at the end. Valid when C | 2048
+//    (every ResNet/UNet width) and the grid stride is a multiple of C, which
+//    grid_quantum() guarantees.
+//  * statistics are accumulated around a per-channel shift (the first pixel's
+//    value on the fast path, the mean of the first 32 pixels on the generic
+//    one), so the single-pass E[d^2]-E[d]^2 variance does not cancel when
+//    |mean| >> std.
 //  * fusion: the residual add and ReLU fold into the normalize pass (fwd) and
 //    the dgamma/dbeta pass emits the gated upstream gradient (bwd) so the
 //    elementwise add/relu/relu' kernels and their whole-tensor round trips
@@ -73,6 +79,35 @@ struct VecIO<float> {
 // channel slots) and total < 2^31
 // ---------------------------------------------------------------------------
 
+// First channel of this thread's vectors. Vector i starts at channel
+// (i*V) % C; it is the same for every i of the grid-stride loop because the
+// launchers keep gridDim.x * 256 * V a multiple of C. One block row of 256*V
+// elements is a multiple of C for every eligible C except fp32 C=2048, where
+// it is half of C and the block index decides which half.
+template <int V>
+__device__ __forceinline__ u32 channel_slot(u32 C) {
+  return ((blockIdx.x * blockDim.x + threadIdx.x) * (u32)V) % C;
+}
+
+// Per-channel shift the statistics are accumulated around: the mean of the
+// channel's first n pixels, added up in index order by ONE thread, so that the
+// stage-A kernels and stats_merge_finalize arrive at the same bits. n = 1 (the
+// first pixel itself) on the fast path, where every thread needs the shift of
+// its own channels; min(M, 32) on the generic path, where one thread per block
+// computes it: the closer the shift is to the mean, the less E[d^2] exceeds
+// the variance and the less of its rounding error the subtraction magnifies.
+#define TFOSR_BN_SHIFT_PIXELS 32
+
+template <typename T>
+__device__ __forceinline__ float channel_shift(const T* __restrict__ x, int c,
+                                               int C, long HW, bool nhwc,
+                                               int n) {
+  float s = 0.f;
+  for (int m = 0; m < n; ++m)
+    s += (float)x[nhwc ? (long)m * C + c : ((m / HW) * C + c) * HW + m % HW];
+  return s / (float)n;
+}
+
 // Stage A: per-block partials into workspace[block][2C] via an LDS reduce —
 // NO global atomics (a per-thread global-atomic tail serializes ~10^5 adds
 // per channel address and was 40x slower than the loads themselves).
@@ -81,17 +116,18 @@ __global__ void stats_nhwc_fast(const T* __restrict__ x,
                                 float* __restrict__ partials, u32 nvec, u32 C) {
   extern __shared__ float lds[];  // [2C]: sums then sumsqs
   constexpr int V = VecIO<T>::V;
-  const u32 c0 = ((u32)threadIdx.x * V) % C;
+  const u32 c0 = channel_slot<V>(C);
   for (u32 i = threadIdx.x; i < 2 * C; i += blockDim.x) lds[i] = 0.f;
   __syncthreads();
-  float s[V], q[V], v[V];
+  float s[V], q[V], v[V], k[V];
+  VecIO<T>::load(x + c0, k);  // shift: the first pixel of these channels
   #pragma unroll
   for (int j = 0; j < V; ++j) { s[j] = 0.f; q[j] = 0.f; }
   const u32 stride = gridDim.x * blockDim.x;
   for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
     VecIO<T>::load(x + (size_t)i * V, v);
     #pragma unroll
-    for (int j = 0; j < V; ++j) { s[j] += v[j]; q[j] += v[j] * v[j]; }
+    for (int j = 0; j < V; ++j) { float d = v[j] - k[j]; s[j] += d; q[j] += d * d; }
   }
   #pragma unroll
   for (int j = 0; j < V; ++j) {
@@ -104,11 +140,15 @@ __global__ void stats_nhwc_fast(const T* __restrict__ x,
 }
 
 // Stage B: sum partials over blocks + finalize mean/rstd + running stats.
+// The partials are sums of (x - shift) and (x - shift)^2 with shift =
+// channel_shift(..., nshift).
 // One block per channel, 256 threads strided over the partial blocks — a
 // single-block C-thread version serialized ~1000 loads per thread (227 us;
 // 40x this kernel's data).
 __global__ void stats_merge_finalize(const float* __restrict__ partials,
                                      int nblocks, u32 C,
+                                     const void* __restrict__ x, int is_bf16,
+                                     int is_nhwc, long HW, int nshift,
                                      float* __restrict__ save_mean,
                                      float* __restrict__ save_rstd,
                                      float* __restrict__ running_mean,
@@ -125,8 +165,12 @@ __global__ void stats_merge_finalize(const float* __restrict__ partials,
   __syncthreads();
   q = block_sum<256>(q, scratch);
   if (threadIdx.x != 0) return;
-  float mean = s / (float)M;
-  float var = fmaxf(q / (float)M - mean * mean, 0.f);
+  const float shift =
+      is_bf16 ? channel_shift((const bf16_t*)x, (int)c, (int)C, HW, is_nhwc, nshift)
+              : channel_shift((const float*)x, (int)c, (int)C, HW, is_nhwc, nshift);
+  float dmean = s / (float)M;
+  float var = fmaxf(q / (float)M - dmean * dmean, 0.f);
+  float mean = shift + dmean;
   save_mean[c] = mean;
   save_rstd[c] = rsqrtf(var + eps);
   if (running_mean != nullptr) {
@@ -146,12 +190,15 @@ __global__ void bn_apply_fast(const T* __restrict__ x, const T* __restrict__ res
                               const float* __restrict__ w,
                               const float* __restrict__ b, u32 nvec, u32 C) {
   constexpr int V = VecIO<T>::V;
-  const u32 c0 = ((u32)threadIdx.x * V) % C;
-  float sc[V], sh[V], v[V], r[V];
+  const u32 c0 = channel_slot<V>(C);
+  // (x - mean) * scale + bias: subtracting first keeps a channel with a tiny
+  // variance (huge scale) exact where x*scale + (bias - mean*scale) cancels
+  float sc[V], mu[V], sh[V], v[V], r[V];
   #pragma unroll
   for (int j = 0; j < V; ++j) {
     sc[j] = w[c0 + j] * rstd[c0 + j];
-    sh[j] = b[c0 + j] - mean[c0 + j] * sc[j];
+    mu[j] = mean[c0 + j];
+    sh[j] = b[c0 + j];
   }
   const u32 stride = gridDim.x * blockDim.x;
   for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
@@ -160,7 +207,7 @@ __global__ void bn_apply_fast(const T* __restrict__ x, const T* __restrict__ res
     unsigned char m = 0;
     #pragma unroll
     for (int j = 0; j < V; ++j) {
-      float o = v[j] * sc[j] + sh[j];
+      float o = (v[j] - mu[j]) * sc[j] + sh[j];
       if (ADD) o += r[j];
       if (RELU) {
         if (o > 0.f) m |= (1u << j);
@@ -184,7 +231,7 @@ __global__ void bwd_stats_fast(const T* __restrict__ x, const T* __restrict__ dy
                                float* __restrict__ partials, u32 nvec, u32 C) {
   extern __shared__ float lds[];  // [2C]: dgamma then dbeta
   constexpr int V = VecIO<T>::V;
-  const u32 c0 = ((u32)threadIdx.x * V) % C;
+  const u32 c0 = channel_slot<V>(C);
   for (u32 i = threadIdx.x; i < 2 * C; i += blockDim.x) lds[i] = 0.f;
   __syncthreads();
   float sg[V], sb[V], xv[V], dv[V];
@@ -250,7 +297,7 @@ __global__ void bwd_dx_fast(const T* __restrict__ x, const T* __restrict__ dy,
                             const float* __restrict__ db,
                             u32 nvec, u32 C, float invM) {
   constexpr int V = VecIO<T>::V;
-  const u32 c0 = ((u32)threadIdx.x * V) % C;
+  const u32 c0 = channel_slot<V>(C);
   float sc[V], mu[V], rs[V], dgm[V], dbm[V], xv[V], dv[V];
   #pragma unroll
   for (int j = 0; j < V; ++j) {
@@ -278,16 +325,51 @@ __global__ void bwd_dx_fast(const T* __restrict__ x, const T* __restrict__ dy,
 // Generic fallbacks (any layout/shape): scalar, 64-bit safe
 // ---------------------------------------------------------------------------
 
+// The generic reductions give block (c, k) the pixels [k*CHUNK, (k+1)*CHUNK) of
+// channel c (further chunks by grid stride): a register chain of CHUNK/256
+// adds per thread, a tree over the block, then ONE atomic per block and
+// channel into the zeroed workspace. An atomic per element made every channel
+// sum a serial fp32 chain of M adds, whose rounding error grows with M.
+#define TFOSR_BN_CHUNK 4096
+
+template <bool NHWC>
+__device__ __forceinline__ long pixel_index(long m, int c, int C, long HW) {
+  return NHWC ? m * C + c : ((m / HW) * C + c) * HW + m % HW;
+}
+
+static inline dim3 generic_red_grid(long M, int C) {
+  long chunks = (M + TFOSR_BN_CHUNK - 1) / TFOSR_BN_CHUNK;
+  if (chunks > 1024) chunks = 1024;
+  return dim3((unsigned)C, (unsigned)(chunks > 0 ? chunks : 1));
+}
+
 template <typename T, bool NHWC>
 __global__ void stats_generic(const T* __restrict__ x, float* __restrict__ ws,
-                              long total, int C, long HW) {
-  // atomic per element — this path only serves odd shapes/layouts
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    int c = NHWC ? (int)(idx % C) : (int)((idx / HW) % C);
-    float v = (float)x[idx];
-    atomicAdd(&ws[c], v);
-    atomicAdd(&ws[C + c], v * v);
+                              long M, int C, long HW) {
+  __shared__ float scratch[8];
+  __shared__ float shift;
+  const int c = blockIdx.x;
+  if (threadIdx.x == 0)
+    shift = channel_shift(x, c, C, HW, NHWC,
+                          M < TFOSR_BN_SHIFT_PIXELS ? (int)M : TFOSR_BN_SHIFT_PIXELS);
+  __syncthreads();
+  const float k = shift;
+  float s = 0.f, q = 0.f;
+  for (long m0 = (long)blockIdx.y * TFOSR_BN_CHUNK; m0 < M;
+       m0 += (long)gridDim.y * TFOSR_BN_CHUNK) {
+    const long m1 = m0 + TFOSR_BN_CHUNK < M ? m0 + TFOSR_BN_CHUNK : M;
+    for (long m = m0 + threadIdx.x; m < m1; m += blockDim.x) {
+      float d = (float)x[pixel_index<NHWC>(m, c, C, HW)] - k;
+      s += d;
+      q += d * d;
+    }
+  }
+  s = block_sum<256>(s, scratch);
+  __syncthreads();
+  q = block_sum<256>(q, scratch);
+  if (threadIdx.x == 0) {
+    atomicAdd(&ws[c], s);
+    atomicAdd(&ws[C + c], q);
   }
 }
 
@@ -315,15 +397,29 @@ __global__ void bwd_stats_generic(const T* __restrict__ x, const T* __restrict__
                                   const float* __restrict__ mean,
                                   const float* __restrict__ rstd,
                                   float* __restrict__ ws,
-                                  long total, int C, long HW) {
-  for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total;
-       idx += (long)gridDim.x * blockDim.x) {
-    int c = NHWC ? (int)(idx % C) : (int)((idx / HW) % C);
-    float g = (float)dy[idx];
-    if (RELU) g = ((float)y[idx] > 0.f) ? g : 0.f;
-    atomicAdd(&ws[C + c], g);
-    atomicAdd(&ws[c], g * ((float)x[idx] - mean[c]) * rstd[c]);
-    if (WRITE_G) gout[idx] = (T)g;
+                                  long M, int C, long HW) {
+  __shared__ float scratch[8];
+  const int c = blockIdx.x;
+  const float mu = mean[c], rs = rstd[c];
+  float sg = 0.f, sb = 0.f;
+  for (long m0 = (long)blockIdx.y * TFOSR_BN_CHUNK; m0 < M;
+       m0 += (long)gridDim.y * TFOSR_BN_CHUNK) {
+    const long m1 = m0 + TFOSR_BN_CHUNK < M ? m0 + TFOSR_BN_CHUNK : M;
+    for (long m = m0 + threadIdx.x; m < m1; m += blockDim.x) {
+      const long idx = pixel_index<NHWC>(m, c, C, HW);
+      float g = (float)dy[idx];
+      if (RELU) g = ((float)y[idx] > 0.f) ? g : 0.f;
+      sb += g;
+      sg += g * ((float)x[idx] - mu) * rs;
+      if (WRITE_G) gout[idx] = (T)g;
+    }
+  }
+  sg = block_sum<256>(sg, scratch);
+  __syncthreads();
+  sb = block_sum<256>(sb, scratch);
+  if (threadIdx.x == 0) {
+    atomicAdd(&ws[c], sg);
+    atomicAdd(&ws[C + c], sb);
   }
 }
 
@@ -355,18 +451,28 @@ static inline bool fast_ok(int is_nhwc, long total, int C, int vec) {
   return is_nhwc && total < (1L << 31) && C % vec == 0 && 2048 % C == 0;
 }
 
-static inline int fast_grid(long nvec) {
-  long g = (nvec + 255) / 256;
-  if (g > TFOSR_MAX_GRID) g = TFOSR_MAX_GRID;
-  return (int)(g > 0 ? g : 1);
+// The fast kernels need gridDim.x * 256 * vec to be a multiple of C so that a
+// thread's channel slot survives the grid stride: grids are multiples of this
+// (1 for every eligible shape except fp32 C=2048, where it is 2).
+static inline int grid_quantum(int C, int vec) {
+  int row = 256 * vec;
+  return C > row ? C / row : 1;
 }
 
-static inline int red_grid(long nvec) {
+static inline int fast_grid(long nvec, int quantum) {
+  long g = (nvec + 255) / 256;
+  g = (g + quantum - 1) / quantum * quantum;
+  if (g > TFOSR_MAX_GRID) g = TFOSR_MAX_GRID;  // a multiple of every quantum
+  return (int)(g > 0 ? g : quantum);
+}
+
+static inline int red_grid(long nvec, int quantum) {
   // reduction stage A: >=32 vectors per thread bounds the partials traffic
   // to ~3% of the tensor; [64, 1024] keeps the chip busy on small layers
   long g = nvec / (256 * 32);
   if (g < 64) g = 64;
   if (g > 1024) g = 1024;
+  g -= g % quantum;
   return (int)g;
 }
 
@@ -378,7 +484,7 @@ extern "C" {
 int tfosr_bn_fast_blocks(long total, int C, int is_bf16, int is_nhwc) {
   int vec = is_bf16 ? 8 : 4;
   if (!fast_ok(is_nhwc, total, C, vec)) return 0;
-  return red_grid(total / vec);
+  return red_grid(total / vec, grid_quantum(C, vec));
 }
 
 void tfosr_bn_stats(const void* x, int is_bf16, int is_nhwc, float* partials,
@@ -396,19 +502,24 @@ void tfosr_bn_stats(const void* x, int is_bf16, int is_nhwc, float* partials,
                          (const float*)x, partials, nvec, (u32)C);
     return;
   }
-  int grid = tfosr_grid(total, 256);
-#define SG(T, L) hipLaunchKernelGGL((stats_generic<T, L>), dim3(grid), dim3(256), \
-                                    0, s, (const T*)x, partials, total, C, HW)
+  const long M = (long)N * HW;
+  dim3 grid = generic_red_grid(M, C);
+#define SG(T, L) hipLaunchKernelGGL((stats_generic<T, L>), grid, dim3(256), \
+                                    0, s, (const T*)x, partials, M, C, HW)
   if (is_bf16) { if (is_nhwc) SG(bf16_t, true); else SG(bf16_t, false); }
   else { if (is_nhwc) SG(float, true); else SG(float, false); }
 #undef SG
 }
 
-void tfosr_bn_finalize(const float* partials, int nb, float* save_mean,
+// x, is_bf16, is_nhwc, HW: as given to tfosr_bn_stats (locates the shift)
+void tfosr_bn_finalize(const float* partials, int nb, const void* x,
+                       int is_bf16, int is_nhwc, long HW, float* save_mean,
                        float* save_rstd, float* running_mean, float* running_var,
                        long M, int C, float momentum, float eps, hipStream_t s) {
   hipLaunchKernelGGL(stats_merge_finalize, dim3(C), dim3(256), 0, s,
-                     partials, nb > 0 ? nb : 1, (u32)C, save_mean, save_rstd,
+                     partials, nb > 0 ? nb : 1, (u32)C, x, is_bf16, is_nhwc, HW,
+                     nb > 0 ? 1 : (int)(M < TFOSR_BN_SHIFT_PIXELS ? M : TFOSR_BN_SHIFT_PIXELS),
+                     save_mean, save_rstd,
                      running_mean, running_var, M, momentum, eps);
 }
 
@@ -422,7 +533,7 @@ void tfosr_bn_apply(const void* x, const void* res, void* y, unsigned char* mask
   const bool add = res != nullptr;
   if (fast_ok(is_nhwc, total, C, vec)) {
     u32 nvec = (u32)(total / vec);
-    int grid = fast_grid(nvec);
+    int grid = fast_grid(nvec, grid_quantum(C, vec));
 #define APPLY_FAST(T, R, A) \
     hipLaunchKernelGGL((bn_apply_fast<T, R, A>), dim3(grid), dim3(256), 0, s, \
                        (const T*)x, (const T*)res, (T*)y, mask, mean, rstd, w, b, \
@@ -483,11 +594,12 @@ void tfosr_bn_bwd_stats(const void* x, const void* dy, const void* y,
 #undef BS_FAST
     return;
   }
-  int grid = tfosr_grid(total, 256);
+  const long M = (long)N * HW;
+  dim3 grid = generic_red_grid(M, C);
 #define BS_GEN(T, L, R, W) \
-  hipLaunchKernelGGL((bwd_stats_generic<T, L, R, W>), dim3(grid), dim3(256), 0, s, \
+  hipLaunchKernelGGL((bwd_stats_generic<T, L, R, W>), grid, dim3(256), 0, s, \
                      (const T*)x, (const T*)dy, (const T*)y, (T*)gout, \
-                     mean, rstd, partials, total, C, HW)
+                     mean, rstd, partials, M, C, HW)
   if (is_bf16) {
     if (is_nhwc) { if (relu) { if (wg) BS_GEN(bf16_t, true, true, true); else BS_GEN(bf16_t, true, true, false); }
                    else { if (wg) BS_GEN(bf16_t, true, false, true); else BS_GEN(bf16_t, true, false, false); } }
@@ -518,7 +630,7 @@ void tfosr_bn_bwd_dx(const void* x, const void* dy, const void* y,
   int vec = is_bf16 ? 8 : 4;
   if (fast_ok(is_nhwc, total, C, vec)) {
     u32 nvec = (u32)(total / vec);
-    int grid = fast_grid(nvec);
+    int grid = fast_grid(nvec, grid_quantum(C, vec));
 #define DX_FAST(T, R) \
     hipLaunchKernelGGL((bwd_dx_fast<T, R>), dim3(grid), dim3(256), 0, s, \
                        (const T*)x, (const T*)dy, mask, (T*)dx, \

@@ -56,6 +56,27 @@ def test_bn_relu_forward_train(dtype, channels_last):
     _close(rv, rv_ref, 1e-2, 1e-3, "running_var")
     _close(mean, xf.mean(dim=(0, 2, 3)), 1e-3, 1e-4, "save_mean")
 
+    # rstd and the unbiased running_var against plain fp64 arithmetic; bound =
+    # 16 x the error of the same arithmetic in fp32 + half an fp32 ulp
+    # (derivation in test_gpu_bn.py)
+    M = N * H * W
+
+    def stats(dt):
+        xd = x.to(dt)
+        mu = xd.mean(dim=(0, 2, 3), keepdim=True)
+        var = ((xd - mu) ** 2).mean(dim=(0, 2, 3))
+        return (1.0 / torch.sqrt(var + 1e-5),
+                (1 - 0.1) * rv_ref.new_ones(C).to(dt) + 0.1 * (var * M / (M - 1)))
+
+    for what, got, r64, r32 in zip(("save_rstd", "running_var (unbiased)"),
+                                   (rstd, rv), stats(torch.float64),
+                                   stats(torch.float32)):
+        bound = (16 * (r32.double() - r64).abs().max()
+                 + 2.0 ** -24 * r64.abs())
+        err = (got.double() - r64).abs()
+        assert (err <= bound).all(), "{}: err {} vs bound {}".format(
+            what, err.max().item(), bound.min().item())
+
 
 @gpu
 @requires_gpu
