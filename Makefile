@@ -20,6 +20,7 @@ bench-kernels:
 	python tools/conv_bench.py --batch 1024
 	python tools/conv_bench.py --wrw --batch 1024
 	python tools/bn_bench.py --batch 1024
+	python tools/xent_bench.py
 	python tools/bucket_sweep.py --steps 6 --warmup 2
 
 lint:

@@ -24,10 +24,15 @@ void tfosr_bn_bwd_dx(const void*, const void*, const void*,
                      const unsigned char*, const float*,
                      const float*, const float*, const float*, const float*,
                      void*, int, int, int, long, int, long, hipStream_t);
-void tfosr_xent_fwd(const void*, const long*, float*, float*, int, int, int,
-                    hipStream_t);
-void tfosr_xent_bwd(const void*, const float*, const long*, const float*, void*,
-                    int, int, int, hipStream_t);
+int tfosr_xent_dense_grid(int, int, long, long, int, int);
+void tfosr_xent_dense_fwd(int, const void*, const long*, float*, float*, float*,
+                          int*, int, long, long, int, long, float, int,
+                          hipStream_t);
+void tfosr_xent_dense_finalize(const float*, const int*, int, int, float*, int*,
+                               hipStream_t);
+void tfosr_xent_dense_bwd(int, const void*, const float*, const long*,
+                          const float*, const float*, const int*, int, void*,
+                          int, long, long, int, long, float, int, hipStream_t);
 void tfosr_nhwc_pack(const void*, void*, const float*, const float*, float, int,
                      int, long, int, long, hipStream_t);
 void tfosr_sgd_step(float*, const float*, float*, float, float, float, int, long,
@@ -266,26 +271,188 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y,
   return {dx, dg, db};
 }
 
+// ---------------------------------------------------------------------------
+// Dense softmax cross-entropy (csrc/softmax_xent_dense.hip)
+// ---------------------------------------------------------------------------
+
+enum { XENT_ROWS = 0, XENT_STRIDED = 1, XENT_TILE = 2 };
+enum { XENT_NONE = 0, XENT_SUM = 1, XENT_MEAN = 2 };
+
+// How the kernels see the logits: P rows or pixels of C classes; S is the
+// class stride of the strided family (1 for class-contiguous rows).
+struct XentLayout {
+  int family;
+  long P, S;
+  int C;
+};
+
+// logits (P, C) with target (P,), or (N, C, d1, ...) with target
+// (N, d1, ...). No layout makes a copy: class-contiguous rows (2-D, or 4-D
+// channels_last through its flat view) go to the row-per-block kernels for
+// C >= 64 and to the LDS-tile kernels below that; standard-contiguous N-D
+// logits go to the class-strided kernels.
+XentLayout xent_layout(const at::Tensor& logits, const at::Tensor& target) {
+  TORCH_CHECK(logits.is_cuda(), "xent: logits must be a GPU tensor");
+  TORCH_CHECK(logits.scalar_type() == at::kFloat ||
+                  logits.scalar_type() == at::kBFloat16,
+              "xent: logits must be float32 or bfloat16");
+  TORCH_CHECK(logits.dim() >= 2, "xent: logits must be (P, C) or (N, C, d1, ...)");
+  TORCH_CHECK(target.device() == logits.device(),
+              "xent: target must be on ", logits.device());
+  TORCH_CHECK(target.scalar_type() == at::kLong, "xent: target must be int64");
+  TORCH_CHECK(target.is_contiguous(), "xent: target must be contiguous");
+  TORCH_CHECK(target.dim() == logits.dim() - 1 &&
+                  target.size(0) == logits.size(0),
+              "xent: target must have the logits' shape without the class dim");
+  for (int64_t d = 2; d < logits.dim(); ++d)
+    TORCH_CHECK(target.size(d - 1) == logits.size(d),
+                "xent: target must have the logits' shape without the class dim");
+  TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) < (1L << 24),
+              "xent: bad class count");
+  XentLayout l;
+  l.C = (int)logits.size(1);
+  l.P = target.numel();
+  l.S = 1;
+  bool rows;
+  if (logits.dim() == 2) {
+    TORCH_CHECK(logits.is_contiguous(), "xent: 2-D logits must be contiguous");
+    rows = true;
+  } else if (logits.is_contiguous()) {
+    rows = false;
+    for (int64_t d = 2; d < logits.dim(); ++d) l.S *= logits.size(d);
+  } else {
+    TORCH_CHECK(logits.dim() == 4 &&
+                    logits.is_contiguous(at::MemoryFormat::ChannelsLast),
+                "xent: N-D logits must be contiguous or 4-D channels_last");
+    rows = true;
+  }
+  l.family = rows ? (l.C >= 64 ? XENT_ROWS : XENT_TILE) : XENT_STRIDED;
+  return l;
+}
+
+void xent_check_rowvec(const at::Tensor& t, const at::Tensor& logits, long P,
+                       const char* name) {
+  TORCH_CHECK(t.device() == logits.device() && t.scalar_type() == at::kFloat &&
+                  t.is_contiguous() && t.numel() == P,
+              "xent: ", name, " must be contiguous float32 with one value per "
+              "row, on the logits' device");
+}
+
+// reduction 0 none / 1 sum / 2 mean. Returns {loss, lse, n_valid}: loss has
+// the target's shape for none and is a 0-dim device scalar otherwise;
+// n_valid (int32[1], device) is empty for none. max_grid 0 = project cap.
+std::vector<at::Tensor> xent_dense_fwd(at::Tensor logits, at::Tensor target,
+                                       long ignore_index, double label_smoothing,
+                                       long reduction, long max_grid) {
+  auto l = xent_layout(logits, target);
+  TORCH_CHECK(reduction >= XENT_NONE && reduction <= XENT_MEAN,
+              "xent: reduction must be 0 (none), 1 (sum) or 2 (mean)");
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing <= 1.0,
+              "xent: label_smoothing must be in [0, 1]");
+  TORCH_CHECK(max_grid >= 0, "xent: max_grid must be >= 0");
+  int bf = dtype_flag(logits);
+  auto fopts = logits.options().dtype(at::kFloat);
+  auto iopts = logits.options().dtype(at::kInt);
+  auto lse = at::empty({l.P}, fopts);
+  auto s = cur_stream();
+  if (reduction == XENT_NONE) {
+    auto loss = at::empty(target.sizes(), fopts);
+    tfosr_xent_dense_fwd(l.family, logits.data_ptr(), target.data_ptr<long>(),
+                         loss.data_ptr<float>(), lse.data_ptr<float>(), nullptr,
+                         nullptr, bf, l.P, l.S, l.C, ignore_index,
+                         (float)label_smoothing, (int)max_grid, s);
+    return {loss, lse, at::empty({0}, iopts)};
+  }
+  auto loss = at::zeros({}, fopts);
+  auto nvalid = at::zeros({1}, iopts);
+  if (l.P > 0) {
+    int nb = tfosr_xent_dense_grid(l.family, bf, l.P, l.S, l.C, (int)max_grid);
+    auto part_loss = at::empty({2L * nb}, fopts);
+    auto part_cnt = at::empty({nb}, iopts);
+    tfosr_xent_dense_fwd(l.family, logits.data_ptr(), target.data_ptr<long>(),
+                         nullptr, lse.data_ptr<float>(),
+                         part_loss.data_ptr<float>(), part_cnt.data_ptr<int>(),
+                         bf, l.P, l.S, l.C, ignore_index,
+                         (float)label_smoothing, (int)max_grid, s);
+    tfosr_xent_dense_finalize(part_loss.data_ptr<float>(),
+                              part_cnt.data_ptr<int>(), nb,
+                              reduction == XENT_MEAN, loss.data_ptr<float>(),
+                              nvalid.data_ptr<int>(), s);
+  }
+  return {loss, lse, nvalid};
+}
+
+// gout: per-row upstream gradient (none, the target's shape) or a one-element
+// device scalar (sum / mean, with the forward's n_valid).
+at::Tensor xent_dense_bwd(at::Tensor logits, at::Tensor lse, at::Tensor target,
+                          at::Tensor gout, c10::optional<at::Tensor> nvalid,
+                          long ignore_index, double label_smoothing,
+                          long reduction, long max_grid) {
+  auto l = xent_layout(logits, target);
+  TORCH_CHECK(reduction >= XENT_NONE && reduction <= XENT_MEAN,
+              "xent: reduction must be 0 (none), 1 (sum) or 2 (mean)");
+  TORCH_CHECK(max_grid >= 0, "xent: max_grid must be >= 0");
+  int bf = dtype_flag(logits);
+  xent_check_rowvec(lse, logits, l.P, "lse");
+  const float* grows = nullptr;
+  const float* gscalar = nullptr;
+  const int* nv = nullptr;
+  if (reduction == XENT_NONE) {
+    xent_check_rowvec(gout, logits, l.P, "gout");
+    grows = gout.data_ptr<float>();
+  } else {
+    TORCH_CHECK(gout.device() == logits.device() &&
+                    gout.scalar_type() == at::kFloat && gout.numel() == 1,
+                "xent: gout must be a one-element float32 device tensor");
+    TORCH_CHECK(nvalid.has_value() && nvalid->device() == logits.device() &&
+                    nvalid->scalar_type() == at::kInt && nvalid->numel() == 1,
+                "xent: n_valid must be the int32[1] tensor the forward returned");
+    gscalar = gout.data_ptr<float>();
+    nv = nvalid->data_ptr<int>();
+  }
+  // same sizes and strides as the logits
+  auto dlogits = at::empty_like(logits);
+  tfosr_xent_dense_bwd(l.family, logits.data_ptr(), lse.data_ptr<float>(),
+                       target.data_ptr<long>(), grows, gscalar, nv,
+                       reduction == XENT_MEAN, dlogits.data_ptr(), bf, l.P, l.S,
+                       l.C, ignore_index, (float)label_smoothing, (int)max_grid,
+                       cur_stream());
+  return dlogits;
+}
+
+// Plain 2-D entry points for callers of the extension: per-row loss, no
+// ignore_index or smoothing, row-per-block kernels for every C.
 std::vector<at::Tensor> softmax_xent_fwd(at::Tensor logits, at::Tensor target) {
   TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous());
-  TORCH_CHECK(target.scalar_type() == at::kLong);
-  int N = logits.size(0), C = logits.size(1);
+  TORCH_CHECK(target.scalar_type() == at::kLong && target.is_cuda() &&
+              target.is_contiguous() && target.numel() == logits.size(0));
+  long N = logits.size(0);
+  int C = logits.size(1);
   auto opts = logits.options().dtype(at::kFloat);
   auto loss = at::empty({N}, opts);
   auto lse = at::empty({N}, opts);
-  tfosr_xent_fwd(logits.data_ptr(), target.data_ptr<long>(),
-                 loss.data_ptr<float>(), lse.data_ptr<float>(),
-                 dtype_flag(logits), N, C, cur_stream());
+  tfosr_xent_dense_fwd(XENT_ROWS, logits.data_ptr(), target.data_ptr<long>(),
+                       loss.data_ptr<float>(), lse.data_ptr<float>(), nullptr,
+                       nullptr, dtype_flag(logits), N, 1, C, -100, 0.f, 0,
+                       cur_stream());
   return {loss, lse};
 }
 
 at::Tensor softmax_xent_bwd(at::Tensor logits, at::Tensor lse, at::Tensor target,
                             at::Tensor gout) {
-  int N = logits.size(0), C = logits.size(1);
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous());
+  TORCH_CHECK(target.scalar_type() == at::kLong && target.is_cuda() &&
+              target.is_contiguous() && target.numel() == logits.size(0));
+  long N = logits.size(0);
+  int C = logits.size(1);
+  gout = gout.contiguous();
+  xent_check_rowvec(lse, logits, N, "lse");
+  xent_check_rowvec(gout, logits, N, "gout");
   auto dlogits = at::empty_like(logits);
-  tfosr_xent_bwd(logits.data_ptr(), lse.data_ptr<float>(),
-                 target.data_ptr<long>(), gout.contiguous().data_ptr<float>(),
-                 dlogits.data_ptr(), dtype_flag(logits), N, C, cur_stream());
+  tfosr_xent_dense_bwd(XENT_ROWS, logits.data_ptr(), lse.data_ptr<float>(),
+                       target.data_ptr<long>(), gout.data_ptr<float>(), nullptr,
+                       nullptr, 0, dlogits.data_ptr(), dtype_flag(logits), N, 1,
+                       C, -100, 0.f, 0, cur_stream());
   return dlogits;
 }
 
@@ -359,7 +526,7 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 4
+#define TFOSR_API_VERSION 5
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("api_version", []() { return TFOSR_API_VERSION; });
@@ -368,6 +535,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd", &bn_bwd);
   m.def("softmax_xent_fwd", &softmax_xent_fwd);
   m.def("softmax_xent_bwd", &softmax_xent_bwd);
+  m.def("xent_dense_fwd", &xent_dense_fwd, py::arg("logits"), py::arg("target"),
+        py::arg("ignore_index") = -100, py::arg("label_smoothing") = 0.0,
+        py::arg("reduction") = 0, py::arg("max_grid") = 0);
+  m.def("xent_dense_bwd", &xent_dense_bwd, py::arg("logits"), py::arg("lse"),
+        py::arg("target"), py::arg("gout"), py::arg("nvalid") = py::none(),
+        py::arg("ignore_index") = -100, py::arg("label_smoothing") = 0.0,
+        py::arg("reduction") = 0, py::arg("max_grid") = 0);
   m.def("nhwc_pack", &nhwc_pack);
   m.def("sgd_step", &sgd_step);
   m.def("adam_step", [](at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,

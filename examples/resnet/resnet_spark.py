@@ -61,7 +61,8 @@ def map_fun(args, ctx):
         with amp:
             x = nhwc_pack(x_u8, out_dtype=torch.bfloat16 if use_cuda
                           else torch.float32, channels_last=use_cuda)
-            loss = softmax_cross_entropy(model(x), y)
+            loss = softmax_cross_entropy(
+                model(x), y, label_smoothing=args.label_smoothing)
         loss.backward()
         engine.finalize_backward()
         opt.step()
@@ -84,6 +85,8 @@ def main():
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--num_gpus", type=int, default=1)
     p.add_argument("--model_dir", default="resnet_model")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="0.1 in the standard ResNet-50/ImageNet recipe")
     args = p.parse_args()
     # executor working dirs differ from the driver's: path args
     # must be absolute (shared-filesystem semantics, as on a real

@@ -11,6 +11,8 @@ import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
 
+VOID = 255  # mask label of pixels that belong to no class
+
 
 def map_fun(args, ctx):
     import numpy as np
@@ -47,10 +49,9 @@ def map_fun(args, ctx):
         with amp:
             x = nhwc_pack(x_u8, out_dtype=torch.bfloat16 if use_cuda
                           else torch.float32, channels_last=use_cuda)
-            logits = model(x)
-            c = logits.shape[1]
-            loss = softmax_cross_entropy(
-                logits.permute(0, 2, 3, 1).reshape(-1, c), y.reshape(-1))
+            # (N, C, H, W) logits go in as they are; void pixels (255, as on
+            # VOC) add neither loss nor gradient
+            loss = softmax_cross_entropy(model(x), y, ignore_index=VOID)
         loss.backward()
         engine.finalize_backward()
         opt.step()
@@ -87,6 +88,9 @@ def main():
         img = rng.integers(0, 256, size=(128, 128, 3), dtype=np.uint8)
         mask = (img[:, :, 0] > 170).astype(np.int64) + \
                (img[:, :, 0] > 85).astype(np.int64)
+        # a void border, like the unlabelled object outlines of VOC/pets
+        mask[:2, :] = mask[-2:, :] = VOID
+        mask[:, :2] = mask[:, -2:] = VOID
         rows.append((img.reshape(-1), mask.reshape(-1)))
 
     cluster = TFCluster.run(sc, map_fun, args, args.cluster_size,

@@ -133,38 +133,144 @@ class FusedBNAddReLU(FusedBNReLU):
 
 
 # ---------------------------------------------------------------------------
-# Fused softmax cross-entropy (sparse labels)
+# Fused softmax cross-entropy (sparse labels, ignore_index, label smoothing)
 # ---------------------------------------------------------------------------
 
-class _SoftmaxXentFn(torch.autograd.Function):
+_XENT_REDUCTIONS = {"none": 0, "sum": 1, "mean": 2}
+
+
+class _XentNoneFn(torch.autograd.Function):
+    """Per-row loss; backward recomputes the softmax from the saved lse."""
+
     @staticmethod
-    def forward(ctx, logits, target):
+    def forward(ctx, logits, target, ignore_index, label_smoothing):
         ext = get_ext(required=True)
-        loss, lse = ext.softmax_xent_fwd(logits, target)
+        loss, lse, _ = ext.xent_dense_fwd(logits, target, ignore_index,
+                                          label_smoothing, 0, 0)
         ctx.save_for_backward(logits, lse, target)
+        ctx.args = (ignore_index, label_smoothing)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         ext = get_ext(required=True)
         logits, lse, target = ctx.saved_tensors
-        dlogits = ext.softmax_xent_bwd(logits, lse, target, grad_out.contiguous())
-        return dlogits, None
+        dlogits = ext.xent_dense_bwd(logits, lse, target,
+                                     grad_out.float().contiguous(), None,
+                                     ctx.args[0], ctx.args[1], 0, 0)
+        return dlogits, None, None, None
 
 
-def softmax_cross_entropy(logits, target, reduction="mean"):
-    """Sparse softmax cross-entropy (reference workloads:
-    ``sparse_categorical_crossentropy``, e.g. ``mnist_spark.py:22``,
-    ``resnet_cifar_dist.py:210``). Fused single-pass kernel on GPU."""
-    if logits.is_cuda and logits.shape[1] >= 64 and get_ext(required=True) is not None:
-        loss = _SoftmaxXentFn.apply(logits.contiguous(), target.contiguous())
-    else:
-        loss = F.cross_entropy(logits.float(), target, reduction="none")
-    if reduction == "mean":
-        return loss.mean()
+class _XentReducedFn(torch.autograd.Function):
+    """sum / mean without a per-row loss tensor: the forward leaves the loss
+    and the valid-row count on the device, and the backward kernel reads the
+    upstream scalar and the count from there."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, label_smoothing, reduction):
+        ext = get_ext(required=True)
+        loss, lse, nvalid = ext.xent_dense_fwd(logits, target, ignore_index,
+                                               label_smoothing, reduction, 0)
+        ctx.save_for_backward(logits, lse, target, nvalid)
+        ctx.args = (ignore_index, label_smoothing, reduction)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ext = get_ext(required=True)
+        logits, lse, target, nvalid = ctx.saved_tensors
+        dlogits = ext.xent_dense_bwd(logits, lse, target, grad_out.float(),
+                                     nvalid, ctx.args[0], ctx.args[1],
+                                     ctx.args[2], 0)
+        return dlogits, None, None, None, None
+
+
+def _xent_cpu(logits, target, reduction, ignore_index, label_smoothing):
+    """Plain PyTorch: F.cross_entropy plus the two documented deviations."""
+    c = logits.shape[1]
+    x = logits if logits.dtype in (torch.float32, torch.float64) \
+        else logits.float()
+    out_of_range = (target < 0) | (target >= c)
+    target = torch.where(out_of_range, torch.full_like(target, ignore_index),
+                         target)
+    loss = F.cross_entropy(x, target, reduction="none",
+                           ignore_index=ignore_index,
+                           label_smoothing=label_smoothing)
+    if reduction == "none":
+        return loss
     if reduction == "sum":
         return loss.sum()
-    return loss
+    nvalid = (target != ignore_index).sum()
+    return loss.sum() / nvalid.clamp(min=1).to(loss.dtype)
+
+
+def softmax_cross_entropy(logits, target, reduction="mean", ignore_index=-100,
+                          label_smoothing=0.0):
+    """Sparse softmax cross-entropy (reference workloads:
+    ``sparse_categorical_crossentropy``, e.g. ``mnist_spark.py:22``,
+    ``resnet_cifar_dist.py:210``), with the arguments and semantics of
+    ``F.cross_entropy``.
+
+    ``logits`` is ``(P, C)`` with ``target`` ``(P,)``, or ``(N, C, d1, ...)``
+    with ``target`` ``(N, d1, ...)``. On the GPU every shape runs on the
+    gfx950 kernels of ``csrc/softmax_xent_dense.hip`` without a copy of the
+    logits (2-D, standard-contiguous N-D and channels_last 4-D; any other
+    striding is made contiguous first) and without a host synchronisation.
+    The loss is fp32.
+
+    Two deliberate deviations from ``F.cross_entropy``, on CPU and GPU alike:
+
+    * ``mean`` over a batch in which every row is ignored is 0 with all-zero
+      gradients (torch: NaN), so one all-void batch cannot poison a gradient
+      all-reduce;
+    * a target outside ``[0, C)`` that is not ``ignore_index`` is treated as
+      ignored (torch: device assert); no kernel indexes the logits with it.
+    """
+    if reduction not in _XENT_REDUCTIONS:
+        raise ValueError("reduction must be 'none', 'sum' or 'mean', got {!r}"
+                         .format(reduction))
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError("label_smoothing must be in [0, 1], got {}"
+                         .format(label_smoothing))
+    if logits.dim() < 2 or target.dim() != logits.dim() - 1:
+        raise ValueError("expected logits (P, C) or (N, C, d1, ...) and a "
+                         "target without the class dimension")
+    ignore_index = int(ignore_index)
+    label_smoothing = float(label_smoothing)
+    if not logits.is_cuda:
+        return _xent_cpu(logits, target, reduction, ignore_index,
+                         label_smoothing)
+    get_ext(required=True)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        logits = logits.float()
+    if not (logits.is_contiguous() or (
+            logits.dim() == 4
+            and logits.is_contiguous(memory_format=torch.channels_last))):
+        logits = logits.contiguous()
+    target = target.contiguous()
+    if reduction == "none":
+        return _XentNoneFn.apply(logits, target, ignore_index, label_smoothing)
+    return _XentReducedFn.apply(logits, target, ignore_index, label_smoothing,
+                                _XENT_REDUCTIONS[reduction])
+
+
+class SoftmaxCrossEntropy(nn.Module):
+    """Module form of :func:`softmax_cross_entropy` (same arguments)."""
+
+    def __init__(self, reduction="mean", ignore_index=-100,
+                 label_smoothing=0.0):
+        super().__init__()
+        self.reduction = reduction
+        self.ignore_index = ignore_index
+        self.label_smoothing = label_smoothing
+
+    def forward(self, logits, target):
+        return softmax_cross_entropy(logits, target, self.reduction,
+                                     self.ignore_index, self.label_smoothing)
+
+    def extra_repr(self):
+        return "reduction={}, ignore_index={}, label_smoothing={}".format(
+            self.reduction, self.ignore_index, self.label_smoothing)
 
 
 # ---------------------------------------------------------------------------
