@@ -640,17 +640,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                     S, P, taps, fw, D, 1, cur_stream());
     return out;
   });
-  // gemm accumulating into an existing [M, N] tensor: C += A @ B^T
+  // gemm accumulating into an existing [M, N] tensor: C += A @ B^T.
+  // bf16 only: the launcher instantiates the accumulating epilogue for bf16
+  // output alone, so an fp32 c would be overwritten instead of added to.
   m.def("gemm_bt_acc", [](at::Tensor a, at::Tensor b, at::Tensor c) {
-    TORCH_CHECK(a.is_contiguous() && b.is_contiguous() && c.is_contiguous());
+    TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && c.dim() == 2,
+                "gemm_bt_acc: A[M,K], B[N,K], C[M,N] must be 2-D");
+    TORCH_CHECK(a.is_cuda(), "gemm_bt_acc: a must be a GPU tensor");
+    TORCH_CHECK(b.device() == a.device() && c.device() == a.device(),
+                "gemm_bt_acc: b and c must be on ", a.device());
+    TORCH_CHECK(a.is_contiguous() && b.is_contiguous() && c.is_contiguous(),
+                "gemm_bt_acc: a, b and c must be contiguous");
     TORCH_CHECK(a.scalar_type() == at::kBFloat16 &&
-                b.scalar_type() == at::kBFloat16);
+                    b.scalar_type() == at::kBFloat16 &&
+                    c.scalar_type() == at::kBFloat16,
+                "gemm_bt_acc: a, b and c must be bfloat16");
     long M = a.size(0), K = a.size(1), Nn = b.size(0);
-    TORCH_CHECK(b.size(1) == K && c.size(0) == M && c.size(1) == Nn);
-    TORCH_CHECK(K % 32 == 0);
+    TORCH_CHECK(b.size(1) == K && c.size(0) == M && c.size(1) == Nn,
+                "gemm_bt_acc: A[M,K], B[N,K], C[M,N]");
+    TORCH_CHECK(K % 32 == 0, "gemm_bt_acc: K must be a multiple of 32");
     tfosr_gemm_bt_acc(a.data_ptr(), b.data_ptr(), c.data_ptr(),
-                      c.scalar_type() == at::kBFloat16 ? 1 : 0, M, Nn, K, 1,
-                      cur_stream());
+                      /*out_bf16=*/1, M, Nn, K, 1, cur_stream());
     return c;
   });
   // wrw v2: MFMA + hardware transpose-reads + split-M workspace.

@@ -20,12 +20,15 @@ def _close(a, b, rtol, atol, what=""):
         "{}: max abs err {} (ref scale {})".format(what, err, scale)
 
 
-def _conv_case(module, x, ref_fn, w_attr="weight", rtol=3e-2, atol=3e-1):
+def _conv_case(module, x, ref_fn, w_attr="weight", rtol=3e-2, atol=3e-1,
+               grad_fn=None):
     """Run fused module fwd/bwd on bf16 GPU vs fp32 torch reference."""
     xg = x.cuda().to(torch.bfloat16) \
         .contiguous(memory_format=torch.channels_last).requires_grad_(True)
     m = module.cuda()
     y = m(xg)
+    if grad_fn is not None:     # the in-tree autograd Function really ran
+        assert type(y.grad_fn).__name__ == grad_fn
     dy = torch.randn_like(y)
     y.backward(dy)
 
@@ -73,13 +76,17 @@ def test_conv1x1_stride2(shape):
 def test_conv_transpose2d(k, pad, opad):
     from tensorflowonspark_amd.ops.modules import ConvTranspose2dMFMA
     torch.manual_seed(2)
-    N, Cin, H, W, Cout = 2, 64, 8, 8, 96
+    # large enough for ConvTranspose2dMFMA.forward's size gate, which
+    # _eligible does not include: a smaller input runs the library conv
+    N, Cin, H, W, Cout = 2, 64, 64, 64, 96
+    assert N * H * W * 4 >= 32768
     x = torch.randn(N, Cin, H, W)
     m = ConvTranspose2dMFMA(Cin, Cout, k, stride=2, padding=pad,
                             output_padding=opad)
     assert m._eligible
     _conv_case(m, x, lambda xr, wr: F.conv_transpose2d(
-        xr, wr, stride=2, padding=pad, output_padding=opad))
+        xr, wr, stride=2, padding=pad, output_padding=opad),
+        grad_fn="_ConvT2dFnBackward")
 
 
 @gpu
