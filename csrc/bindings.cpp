@@ -52,13 +52,13 @@ void tfosr_conv3x3(const void*, const void*, const void*, void*, int, int, int,
                    int, int, int, int, int, int, int, hipStream_t);
 void tfosr_conv_mfma(const void*, const void*, const void*, void*, int, int,
                      int, int, int, int, int, int, int, int, int, int, int,
-                     int, hipStream_t);
+                     int, int, hipStream_t);
 void tfosr_conv_wrw(const void*, const void*, float*, int, int, int, int, int,
                     int, int, int, int, int, hipStream_t);
 int tfosr_wrw2_split(int, int, long);
 void tfosr_conv_wrw2(const void*, const void*, const void*, float*, float*,
                      int, int, int, int, int, int, int, int, int, int, int,
-                     int, hipStream_t);
+                     int, int, hipStream_t);
 void tfosr_conv_stem(const void*, const void*, const void*, void*, int, int,
                      int, int, int, int, hipStream_t);
 void tfosr_conv_par(const void*, const void*, const void*, void*, int, int,
@@ -526,7 +526,13 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 5
+#define TFOSR_API_VERSION 6
+
+// Largest filter reach fd*(k-1) the conv entries accept. The kernels form
+// ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
+// tensor that fits the device, so a reach capped at 2^20 keeps every such
+// sum far inside the int range.
+static constexpr long kMaxTapReach = 1L << 20;
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("api_version", []() { return TFOSR_API_VERSION; });
@@ -592,31 +598,56 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // explicit because backward-data output size is not derivable from the
   // stored input dims. One kernel covers conv1x1/conv3x3 fwd at stride 1/2,
   // their backward-data, and ConvTranspose2d k3 s2 (survey §2.3 rows 1-2).
+  //
+  // fd is the FILTER dilation (atrous conv): tap (r, s) reads the input at
+  // offset (r*fd, s*fd), so the natural output size is
+  // (H + 2P - fd*(fh-1) - 1)/S + 1. out_f32 returns the fp32 accumulator
+  // unrounded instead of bf16.
   m.def("conv_mfma", [](at::Tensor x, at::Tensor wk, long Cout, long fh,
-                        long fw, long S, long P, long D, long OH, long OW) {
+                        long fw, long S, long P, long D, long OH, long OW,
+                        long fd, bool out_f32) {
     TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
                 "conv_mfma expects channels_last input");
     TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
                 wk.scalar_type() == at::kBFloat16);
     TORCH_CHECK(fh >= 1 && fw >= 1 && fh * fw <= 49, "bad filter dims");
     TORCH_CHECK(D == 1 || D == 2, "input dilation must be 1 or 2");
+    TORCH_CHECK(fd >= 1, "conv_mfma: filter dilation fd must be >= 1, got ",
+                fd);
+    TORCH_CHECK(fd == 1 || D == 1,
+                "conv_mfma: filter dilation fd > 1 requires input dilation "
+                "D == 1");
+    // ih = oh*S - P + r*fd is computed in int: keep the tap reach far
+    // below 2^31 so it cannot overflow whatever the image size
+    TORCH_CHECK(fd <= kMaxTapReach && fd * (fh - 1) <= kMaxTapReach &&
+                    fd * (fw - 1) <= kMaxTapReach,
+                "conv_mfma: fd, fd*(fh-1) and fd*(fw-1) must be <= ",
+                kMaxTapReach);
     long taps = fh * fw;
     int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
     TORCH_CHECK(Cin % 32 == 0, "conv_mfma requires Cin % 32 == 0");
     TORCH_CHECK(wk.size(1) == taps * Cin);
     if (OH < 0) {
       long HV = (H - 1) * D + 1, WV = (W - 1) * D + 1;
-      OH = (HV + 2 * P - fh) / S + 1;
-      OW = (WV + 2 * P - fw) / S + 1;
+      long nh = HV + 2 * P - fd * (fh - 1) - 1;
+      long nw = WV + 2 * P - fd * (fw - 1) - 1;
+      TORCH_CHECK(nh >= 0 && nw >= 0,
+                  "conv_mfma: the dilated filter does not fit the padded "
+                  "input");
+      OH = nh / S + 1;
+      OW = nw / S + 1;
     }
-    auto y = at::empty({N, Cout, OH, OW}, x.options(),
+    auto y = at::empty({N, Cout, OH, OW},
+                       x.options().dtype(out_f32 ? at::kFloat : at::kBFloat16),
                        at::MemoryFormat::ChannelsLast);
     auto guard = at::zeros({64}, x.options());
     tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard.data_ptr(),
-                    y.data_ptr(), /*out_bf16=*/1, N, H, W, Cin, Cout, OH, OW,
-                    S, P, taps, fw, D, 0, cur_stream());
+                    y.data_ptr(), /*out_bf16=*/out_f32 ? 0 : 1, N, H, W, Cin,
+                    Cout, OH, OW, S, P, taps, fw, D, 0, (int)fd, cur_stream());
     return y;
-  });
+  }, py::arg("x"), py::arg("wk"), py::arg("Cout"), py::arg("fh"),
+     py::arg("fw"), py::arg("S"), py::arg("P"), py::arg("D"), py::arg("OH"),
+     py::arg("OW"), py::arg("fd") = 1, py::arg("out_f32") = false);
   // conv_mfma accumulating INTO an existing channels_last tensor:
   // out += conv(x, wk) — fuses the residual-join gradient accumulation the
   // eager autograd would do as a separate whole-tensor add (8.4 ms/step of
@@ -637,7 +668,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     auto guard = at::zeros({64}, x.options());
     tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard.data_ptr(),
                     out.data_ptr(), /*out_bf16=*/1, N, H, W, Cin, Cout, OH, OW,
-                    S, P, taps, fw, D, 1, cur_stream());
+                    S, P, taps, fw, D, 1, /*fd=*/1, cur_stream());
     return out;
   });
   // gemm accumulating into an existing [M, N] tensor: C += A @ B^T.
@@ -666,8 +697,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // wrw v2: MFMA + hardware transpose-reads + split-M workspace.
   // dy [N,Cout,OH,OW] cl, x [N,Cin,H,W] cl; filter R x S_f, conv stride,
   // pad P. Returns fp32 dW [Cout, R*S_f*Cin].
+  // fd: filter dilation of the 3x3 case (dW tap (r, s) pairs dy[oh, ow]
+  // with x[oh*stride - P + r*fd, ow*stride - P + s*fd]).
   m.def("conv_wrw2", [](at::Tensor dy, at::Tensor x, long R, long S_f,
-                        long stride, long P) {
+                        long stride, long P, long fd) {
     TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
                 x.is_contiguous(at::MemoryFormat::ChannelsLast));
     TORCH_CHECK(dy.scalar_type() == at::kBFloat16 &&
@@ -678,6 +711,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                 "conv_wrw2 needs channel counts % 8 == 0");
     long taps = R * S_f;
     TORCH_CHECK(taps == 1 || taps == 9, "conv_wrw2 supports 1x1 and 3x3");
+    TORCH_CHECK(fd >= 1, "conv_wrw2: filter dilation fd must be >= 1, got ",
+                fd);
+    TORCH_CHECK(taps != 1 || fd == 1,
+                "conv_wrw2: a 1x1 filter has no dilation, fd must be 1");
+    TORCH_CHECK(fd <= kMaxTapReach && fd * (R - 1) <= kMaxTapReach &&
+                    fd * (S_f - 1) <= kMaxTapReach,
+                "conv_wrw2: fd, fd*(R-1) and fd*(S_f-1) must be <= ",
+                kMaxTapReach);
     long M = (long)N * OH * OW;
     int split = tfosr_wrw2_split(Cout, Cin, M);
     long K = taps * (long)Cin;
@@ -687,9 +728,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     auto guard = at::zeros({64}, x.options());
     tfosr_conv_wrw2(dy.data_ptr(), x.data_ptr(), guard.data_ptr(),
                     ws.data_ptr<float>(), dW.data_ptr<float>(), N, H, W, Cin,
-                    Cout, OH, OW, R, S_f, stride, P, split, cur_stream());
+                    Cout, OH, OW, R, S_f, stride, P, split, (int)fd,
+                    cur_stream());
     return dW;
-  });
+  }, py::arg("dy"), py::arg("x"), py::arg("R"), py::arg("S_f"),
+     py::arg("stride"), py::arg("P"), py::arg("fd") = 1);
   // One parity class of a stride-2 backward-data / transposed conv:
   // out[oh*2+oh0, ow*2+ow0] = conv(x, wk_class) with the class's taps
   // (list of (r,s) pairs). wk_class: [Cout, ntaps*Cin]. Writes into `out`
@@ -774,7 +817,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     tfosr_conv_wrw2(dy.data_ptr(), x4.data_ptr(), guard.data_ptr(),
                     ws.data_ptr<float>(), dW.data_ptr<float>(), N, Hp, Wp,
                     /*Cin=*/32, Cout, OH, OW, /*R=*/7, /*S_f=*/1,
-                    /*stride=*/2, /*P=*/0, split, cur_stream());
+                    /*stride=*/2, /*P=*/0, split, /*fd=*/1, cur_stream());
     return dW;
   });
   m.def("conv_wrw", [](at::Tensor dy, at::Tensor x, long R, long S, long P) {

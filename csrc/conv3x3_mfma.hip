@@ -23,6 +23,12 @@
 //   - ConvTranspose2d k3 s2       (S=1, D=2, W swapped/flipped)
 // and, with K = 1*Cin (w shaped [Cout, Cin], taps degenerate to r=s=0),
 // 1x1 convolutions at any stride plus their dilated backward-data.
+//
+// Filter dilation fd (runtime, wave-uniform): tap (r, s) reads the input at
+// offset (r*fd, s*fd) — atrous convolution, and its backward-data through
+// the flipped/transposed weight with the same fd. Only the tap offset
+// changes; out-of-image taps still redirect to the guard. Launches with
+// D == 2, PAR or ACC pass fd = 1.
 #include "tfosr_common.h"
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -54,7 +60,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_kernel(
     const bf16_t* __restrict__ guard, OT* __restrict__ C,
     int Nn, int H, int Wd, int Cin, int Cout, int OH, int OW, int S, int P,
     int taps, int fw, int pixst, unsigned long tap_pack, int oh0, int ow0,
-    int OWr, long OHOWr) {
+    int OWr, long OHOWr, int fd) {
   constexpr int BM = WRG * MI * 16;
   constexpr int BN = WCG * 64;
   constexpr int ABYTES = BM * C3_BK * 2;
@@ -117,19 +123,34 @@ __global__ __launch_bounds__(512, 1) void conv3x3_kernel(
               + (sl & 63);
   }
 
+  // K-step -> (tap, cin0) walker. stage_tile is called for kt = 0, 1, 2, ...
+  // in order, so the tap of the next K-step follows from this one's by
+  // wave-uniform adds and compares; t_dh / t_dw are the tap's input offsets
+  // r*fd / s*fd (fd = filter dilation), carried along instead of divided and
+  // multiplied out of kt on every step.
+  int t_rs = 0, t_s = 0, t_dh = 0, t_dw = 0, t_cin0 = 0;
   auto stage_tile = [&](int slot, int kt) {
     const int k0 = kt * C3_BK;
-    const int rs = k0 / Cin;
-    const int rr = PAR ? (int)((tap_pack >> (rs * 8 + 4)) & 15)
-                       : rs / fw;
-    const int ss = PAR ? (int)((tap_pack >> (rs * 8)) & 15)
-                       : rs - (rs / fw) * fw;
-    const int cin0 = k0 - rs * Cin;
+    const int dh = PAR ? (int)((tap_pack >> (t_rs * 8 + 4)) & 15) : t_dh;
+    const int dw = PAR ? (int)((tap_pack >> (t_rs * 8)) & 15) : t_dw;
+    const int cin0 = t_cin0;
+    t_cin0 += C3_BK;
+    if (t_cin0 == Cin) {  // Cin % 32 == 0: a K-step never straddles two taps
+      t_cin0 = 0;
+      ++t_rs;
+      ++t_s;
+      t_dw += fd;
+      if (t_s == fw) {
+        t_s = 0;
+        t_dw = 0;
+        t_dh += fd;
+      }
+    }
     __attribute__((address_space(3))) char* la = lds3 + slot * SLOT;
     __attribute__((address_space(3))) char* lb = la + ABYTES;
     #pragma unroll
     for (int u = 0; u < ACHUNK; ++u) {
-      int ih = a_ohS[u] + rr, iw = a_owS[u] + ss;
+      int ih = a_ohS[u] + dh, iw = a_owS[u] + dw;
       bool ok = a_n[u] >= 0 && ih >= 0 && iw >= 0;
       if (D > 1) {  // dilated input: only multiples of D are stored rows/cols
         ok = ok && (ih % D == 0) && (iw % D == 0);
@@ -230,7 +251,7 @@ template <int D, bool ACC>
 static void launch_conv(const void* X, const void* W9, const void* guard,
                         void* Y, int out_bf16, int N, int H, int W, int Cin,
                         int Cout, int OH, int OW, int S, int P, int taps,
-                        int fw, int pixst, hipStream_t s) {
+                        int fw, int pixst, int fd, hipStream_t s) {
   const long M = (long)N * OH * OW;
   if (Cout >= 192) {
     int ntm = (int)((M + 255) / 256), ntn = (Cout + 255) / 256;
@@ -239,12 +260,14 @@ static void launch_conv(const void* X, const void* W9, const void* guard,
       hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 2, 4, 8, D, ACC>), grid,
                          dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
                          (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
-                         OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW);
+                         OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
+                         fd);
     else
       hipLaunchKernelGGL((conv3x3_kernel<float, 2, 4, 8, D, ACC>), grid,
                          dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
                          (const bf16_t*)guard, (float*)Y, N, H, W, Cin, Cout,
-                         OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW);
+                         OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
+                         fd);
     return;
   }
   int ntm = (int)((M + 255) / 256), ntn = (Cout + 127) / 128;
@@ -253,12 +276,14 @@ static void launch_conv(const void* X, const void* W9, const void* guard,
     hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 4, 2, 4, D, ACC>), grid,
                        dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
                        (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
-                       OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW);
+                       OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
+                         fd);
   else
     hipLaunchKernelGGL((conv3x3_kernel<float, 4, 2, 4, D, ACC>), grid,
                        dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
                        (const bf16_t*)guard, (float*)Y, N, H, W, Cin, Cout,
-                       OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW);
+                       OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
+                         fd);
 }
 
 extern "C" {
@@ -267,28 +292,31 @@ void tfosr_conv3x3(const void* X, const void* W9, const void* guard, void* Y,
                    int out_bf16, int N, int H, int W, int Cin, int Cout,
                    int OH, int OW, int S, int P, hipStream_t s) {
   launch_conv<1, false>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH, OW,
-                        S, P, 9, 3, Cin, s);
+                        S, P, 9, 3, Cin, /*fd=*/1, s);
 }
 
-// General entry: taps = fh*fw; input dilation Dil in {1, 2}
+// General entry: taps = fh*fw; input dilation Dil in {1, 2}; filter dilation
+// fd >= 1 (tap (r, s) reads the input at offset (r*fd, s*fd)). fd > 1 is
+// honoured only by the plain Dil == 1, non-accumulating launch — the binding
+// rejects the other combinations.
 void tfosr_conv_mfma(const void* X, const void* W9, const void* guard, void* Y,
                      int out_bf16, int N, int H, int W, int Cin, int Cout,
                      int OH, int OW, int S, int P, int taps, int fw, int Dil,
-                     int accum, hipStream_t s) {
+                     int accum, int fd, hipStream_t s) {
   if (Dil == 2) {
     if (accum)
       launch_conv<2, true>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH,
-                           OW, S, P, taps, fw, Cin, s);
+                           OW, S, P, taps, fw, Cin, 1, s);
     else
       launch_conv<2, false>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH,
-                            OW, S, P, taps, fw, Cin, s);
+                            OW, S, P, taps, fw, Cin, 1, s);
   } else {
     if (accum)
       launch_conv<1, true>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH,
-                           OW, S, P, taps, fw, Cin, s);
+                           OW, S, P, taps, fw, Cin, 1, s);
     else
       launch_conv<1, false>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH,
-                            OW, S, P, taps, fw, Cin, s);
+                            OW, S, P, taps, fw, Cin, fd, s);
   }
 }
 
@@ -309,13 +337,13 @@ void tfosr_conv_par(const void* X, const void* Wk, const void* guard, void* Y,
                          grid, dim3(512), 0, s, (const bf16_t*)X,
                          (const bf16_t*)Wk, (const bf16_t*)guard, (bf16_t*)Y,
                          N, H, W, Cin, Cout, OHs, OWs, 1, P, ntaps, 1, Cin,
-                         tap_pack, oh0, ow0, OWr, OHOWr);
+                         tap_pack, oh0, ow0, OWr, OHOWr, /*fd=*/1);
     else
       hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 2, 4, 8, 2, false, true>),
                          grid, dim3(512), 0, s, (const bf16_t*)X,
                          (const bf16_t*)Wk, (const bf16_t*)guard, (bf16_t*)Y,
                          N, H, W, Cin, Cout, OHs, OWs, 1, P, ntaps, 1, Cin,
-                         tap_pack, oh0, ow0, OWr, OHOWr);
+                         tap_pack, oh0, ow0, OWr, OHOWr, /*fd=*/1);
     return;
   }
   int ntm = (int)((M + 255) / 256), ntn = (Cout + 127) / 128;
@@ -325,13 +353,13 @@ void tfosr_conv_par(const void* X, const void* Wk, const void* guard, void* Y,
                        dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)Wk,
                        (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
                        OHs, OWs, 1, P, ntaps, 1, Cin, tap_pack, oh0, ow0,
-                       OWr, OHOWr);
+                       OWr, OHOWr, /*fd=*/1);
   else
     hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 4, 2, 4, 2, false, true>), grid,
                        dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)Wk,
                        (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
                        OHs, OWs, 1, P, ntaps, 1, Cin, tap_pack, oh0, ow0,
-                       OWr, OHOWr);
+                       OWr, OHOWr, /*fd=*/1);
 }
 
 // ResNet stem 7x7/s2 forward over a pre-padded NHWC4 image (x4 layout:
@@ -346,7 +374,7 @@ void tfosr_conv_stem(const void* X4, const void* W224, const void* guard,
   // geometry mapped onto the generic kernel: taps=7 rows (fw=1 so rr=rs),
   // S=2, P=0 (pre-padded), "Cin"=32, pixstride=4
   launch_conv<1, false>(X4, W224, guard, Y, /*out_bf16=*/1, N, Hp, Wp, 32,
-                        Cout, OH, OW, 2, 0, 7, 1, 4, s);
+                        Cout, OH, OW, 2, 0, 7, 1, 4, /*fd=*/1, s);
 }
 
 }  // extern "C"

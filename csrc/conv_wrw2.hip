@@ -52,7 +52,8 @@ __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
     const bf16_t* __restrict__ guard, float* __restrict__ ws,
     int Nn, int H, int W, int Cin, int Cout, int OH, int OW, int FW,
     int stride, int P, int pixst, int steps_per_wg, long M,
-    unsigned long magicOW, unsigned long magicOHOW, int ntn, int split) {
+    unsigned long magicOW, unsigned long magicOHOW, int ntn, int split,
+    int fd) {
   constexpr int REG = TAPS + 1;
   constexpr int REGB = 32 * 64 * 2;           // 4 KB per region
   constexpr int SLOT = REG * REGB;
@@ -97,8 +98,8 @@ __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
     int cb = (q >> 6) & 3, h = (q & 1) ^ ((q >> 4) & 1);
     int tap = region - 1;
     ch_isdy[u] = region == 0;
-    ch_r[u] = region ? tap / FW - P : 0;
-    ch_s[u] = region ? tap % FW - P : 0;
+    ch_r[u] = region ? (tap / FW) * fd - P : 0;  // fd: filter dilation
+    ch_s[u] = region ? (tap % FW) * fd - P : 0;
     ch_ldsoff[u] = q * 16;
     int cglob = (region == 0 ? cout0 : cin0) + cb * 16 + h * 8;
     int climit = region == 0 ? Cout : Cin;
@@ -461,7 +462,7 @@ int tfosr_wrw2_split(int Cout, int Cin, long M) {
 void tfosr_conv_wrw2(const void* dy, const void* x, const void* guard,
                      float* ws, float* dW, int N, int H, int W, int Cin,
                      int Cout, int OH, int OW, int R, int S_f, int stride,
-                     int P, int split, hipStream_t s) {
+                     int P, int split, int fd, hipStream_t s) {
   const long M = (long)N * OH * OW;
   const int taps = R * S_f;
   const unsigned long magicOW = (1UL << 40) / (unsigned)OW + 1;
@@ -481,13 +482,13 @@ void tfosr_conv_wrw2(const void* dy, const void* x, const void* guard,
                        (const bf16_t*)dy, (const bf16_t*)x,
                        (const bf16_t*)guard, ws, N, H, W, Cin, Cout, OH, OW,
                        S_f, stride, P, Cin, spw, M, magicOW, magicOHOW, ntn,
-                       split);
+                       split, fd);
   else if (taps == 7)  // stem wrw over the NHWC4 padded view (pixstride 4)
     hipLaunchKernelGGL((conv_wrw2_kernel<7, 2>), grid, block, 0, s,
                        (const bf16_t*)dy, (const bf16_t*)x,
                        (const bf16_t*)guard, ws, N, H, W, Cin, Cout, OH, OW,
                        S_f, stride, P, 4, spw, M, magicOW, magicOHOW, ntn,
-                       split);
+                       split, /*fd=*/1);
   else if (taps == 1)
     hipLaunchKernelGGL((wrw_gemm_tn_kernel<2>), grid, block, 0, s,
                        (const bf16_t*)dy, (const bf16_t*)x,

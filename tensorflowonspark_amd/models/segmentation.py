@@ -15,17 +15,21 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.modules import ConvTranspose2dMFMA, FusedBNReLU
+from ..ops.modules import ConvTranspose2dMFMA, DilatedConv3x3, FusedBNReLU
 from .resnet import Bottleneck, ResNet, _maybe_pack_weights
 
 
 class ConvBNReLU(nn.Sequential):
     def __init__(self, cin, cout, k=3, stride=1, groups=1, dilation=1):
         pad = dilation * (k - 1) // 2
-        super().__init__(
-            nn.Conv2d(cin, cout, k, stride, pad, groups=groups,
-                      dilation=dilation, bias=False),
-            FusedBNReLU(cout))
+        if k == 3 and dilation > 1 and groups == 1 and stride == 1:
+            # atrous 3x3: same parameters and init as the nn.Conv2d below,
+            # routed to the in-tree MFMA kernels (TFOS_ATROUS)
+            conv = DilatedConv3x3(cin, cout, dilation=dilation)
+        else:
+            conv = nn.Conv2d(cin, cout, k, stride, pad, groups=groups,
+                             dilation=dilation, bias=False)
+        super().__init__(conv, FusedBNReLU(cout))
 
 
 class InvertedResidual(nn.Module):
@@ -151,10 +155,10 @@ class DilatedResNet50(ResNet):
     """ResNet-50 with stage-4 stride replaced by dilation (output stride 16).
 
     The stage-4 convs may be the routed MFMA modules (Conv3x3/Conv1x1) —
-    those are converted too: the dilated 3x3 goes back to a library conv
-    (the in-tree kernels do not implement filter dilation), the downsample
-    1x1 just drops its stride, and the whole-block fused path is disabled
-    for these blocks (it assumes undilated convs)."""
+    those are converted too: the dilated 3x3 becomes a DilatedConv3x3 (the
+    implicit-GEMM kernels with a filter dilation, routed by TFOS_ATROUS),
+    the downsample 1x1 just drops its stride, and the whole-block fused path
+    is disabled for these blocks (it assumes undilated convs)."""
 
     def __init__(self):
         super().__init__(Bottleneck, [3, 4, 6, 3], num_classes=1)
@@ -164,8 +168,8 @@ class DilatedResNet50(ResNet):
             blk.stride = 1
             c2 = blk.conv2
             if isinstance(c2, Conv3x3) and c2.stride == 2:
-                new = nn.Conv2d(c2.weight.shape[1], c2.weight.shape[0], 3,
-                                stride=1, padding=2, dilation=2, bias=False)
+                new = DilatedConv3x3(c2.weight.shape[1], c2.weight.shape[0],
+                                     dilation=2)
                 with torch.no_grad():
                     new.weight.copy_(c2.weight)
                 blk.conv2 = new

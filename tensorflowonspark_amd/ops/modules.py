@@ -648,6 +648,216 @@ class Conv3x3(nn.Module):
             self.weight.shape[1], self.weight.shape[0], self.stride)
 
 
+# ---------------------------------------------------------------------------
+# Atrous (filter-dilated) 3x3 convolution on the same implicit-GEMM kernels
+# ---------------------------------------------------------------------------
+
+def live_taps(H, W, k, stride, pad, fd):
+    """Filter taps of a k x k conv with filter dilation ``fd`` that reach at
+    least one input pixel of an H x W image for some output pixel.
+
+    Returns ``(rows, cols)``, two tuples of tap indices. Tap row ``r`` reads
+    input row ``oh*stride - pad + r*fd``; it is dead when that index lies in
+    the padding for every output row ``oh``. Pure Python, no tensor needed.
+    """
+    def axis(L):
+        out_len = (L + 2 * pad - fd * (k - 1) - 1) // stride + 1
+        live = []
+        for t in range(k):
+            c = t * fd - pad
+            # first output index whose read is not left of the image
+            o = 0 if c >= 0 else (-c + stride - 1) // stride
+            if o < out_len and o * stride + c < L:
+                live.append(t)
+        return tuple(live)
+    return axis(H), axis(W)
+
+
+def _atrous_auto(path, M, cin, cout):
+    """TFOS_ATROUS=auto policy: is ``path`` ('fwd', 'dgrad' or 'collapse')
+    of an atrous conv over M = N*H*W pixels routed to the in-tree kernels?
+
+    Follows the isolated measurement at the DeepLabV3 shapes (b32, 32x32
+    map; tools/conv_bench.py --atrous, docs/performance.md "Atrous
+    convolutions"), where a path goes in-tree only if its median, weight
+    re-layout included, was no slower than the library's:
+
+      collapse (rate 36)       7x faster forward, 6x dgrad      -> in-tree
+      512->512 d2   fwd/dgrad  0.17 / 0.19 vs 0.27 / 0.25 ms    -> in-tree
+      2048->256     dgrad      0.33 vs 0.44 ms                  -> in-tree
+      2048->256     fwd        0.54 vs 0.51 ms                  -> library
+
+    The one losing launch is the one with 128 workgroups (256-row x
+    256-column tiles, Cout = 256) on a 256-CU chip; every winning launch
+    has at least 256. That count is the rule, so shapes that were not
+    measured stay on the library unless they fill the chip as well."""
+    if path == "collapse":
+        return True
+    n_out = cout if path == "fwd" else cin
+    tile_n = 256 if n_out >= 192 else 128
+    n_wg = ((M + 255) // 256) * ((n_out + tile_n - 1) // tile_n)
+    return n_wg >= 256
+
+
+def _atrous_route(N, H, W, cin, cout, fd):
+    """(collapse, fwd_in_tree, dgrad_in_tree) for TFOS_ATROUS, or None for
+    the plain library conv."""
+    import os
+    mode = os.environ.get("TFOS_ATROUS", "auto")
+    if mode == "miopen":
+        return None
+    if mode not in ("auto", "mfma"):
+        raise ValueError("TFOS_ATROUS must be auto, mfma or miopen, got "
+                         + repr(mode))
+    centre_only = live_taps(H, W, 3, 1, fd, fd) == ((1,), (1,))
+    if mode == "mfma":
+        return centre_only, True, True
+    M = N * H * W
+    if centre_only and _atrous_auto("collapse", M, cin, cout):
+        return True, True, True
+    fwd = _atrous_auto("fwd", M, cin, cout)
+    dgrad = _atrous_auto("dgrad", M, cin, cout)
+    if not (fwd or dgrad):
+        return None
+    return False, fwd, dgrad
+
+
+class _AtrousConv3x3Fn(torch.autograd.Function):
+    """3x3 conv with filter dilation fd, stride 1, padding fd, on
+    channels_last bf16. Forward is the implicit-GEMM kernel with tap offsets
+    (r*fd, s*fd); dgrad is the SAME kernel run on dy with the flipped and
+    transposed weight, dilation fd and pad 2*fd - fd = fd; wrw is the
+    transpose-read kernel with the same tap offsets when _use_wrw2 routes it
+    in-tree. A direction routed to the library goes through aten."""
+
+    @staticmethod
+    def forward(ctx, x, weight, fd, fwd_in_tree, dgrad_in_tree):
+        ext = get_ext(required=True)
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        if fwd_in_tree:
+            w9 = weight.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin) \
+                .to(torch.bfloat16).contiguous()
+            y = ext.conv_mfma(x, w9, Cout, 3, 3, 1, fd, 1, -1, -1, fd=fd)
+        else:
+            y = F.conv2d(x, weight.to(torch.bfloat16), None, 1, fd, fd)
+        ctx.save_for_backward(x, weight)
+        ctx.fd = fd
+        ctx.dgrad_in_tree = dgrad_in_tree
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = get_ext(required=True)
+        x, weight = ctx.saved_tensors
+        fd = ctx.fd
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        if dy.dtype != torch.bfloat16:
+            dy = dy.to(torch.bfloat16)
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        wrw_in_tree = Cin % 8 == 0 and Cout % 8 == 0 \
+            and _use_wrw2(3, Cin, Cout)
+        dx = dw = None
+        if need_dx and ctx.dgrad_in_tree:
+            # W'[cin][r][s][cout] = W[cout][2-r][2-s][cin]
+            wperm = weight.flip(2, 3).permute(1, 2, 3, 0) \
+                .to(torch.bfloat16).contiguous()
+            dx = ext.conv_mfma(dy, wperm.reshape(Cin, 9 * Cout), Cin, 3, 3,
+                               1, 2 * fd - fd, 1, x.shape[2], x.shape[3],
+                               fd=fd)
+        if need_dw and wrw_in_tree:
+            dw9 = ext.conv_wrw2(dy, x, 3, 3, 1, fd, fd=fd)
+            dw = dw9.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
+        lib_dx = need_dx and dx is None
+        lib_dw = need_dw and dw is None
+        if lib_dx or lib_dw:
+            w4 = weight.to(torch.bfloat16).contiguous(
+                memory_format=torch.channels_last)
+            gx, gw, _ = torch.ops.aten.convolution_backward(
+                dy, x, w4, None, [1, 1], [fd, fd], [fd, fd], False, [0, 0],
+                1, [lib_dx, lib_dw, False])
+            if lib_dx:
+                dx = gx
+            if lib_dw:
+                dw = gw
+        if dw is not None:
+            dw = dw.to(weight.dtype)
+        return dx, dw, None, None, None
+
+
+class _AtrousCollapsedFn(torch.autograd.Function):
+    """Atrous 3x3 conv whose dilation is at least the image size (padding =
+    dilation, stride 1): the eight outer taps only ever read padding, so the
+    conv IS the 1x1 conv of the centre tap. Forward, dgrad and wrw are the
+    Conv1x1 paths on weight[:, :, 1, 1]; dW is exactly zero at the dead
+    taps."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        Cout, Cin = weight.shape[0], weight.shape[1]
+        wc = weight[:, :, 1, 1].contiguous().view(Cout, Cin, 1, 1)
+        return _Conv1x1Fn.forward(ctx, x, wc)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx, dwc = _Conv1x1Fn.backward(ctx, dy)
+        dw = dwc.new_zeros(dwc.shape[0], dwc.shape[1], 3, 3)
+        dw[:, :, 1, 1] = dwc[:, :, 0, 0]
+        return dx, dw
+
+
+class DilatedConv3x3(nn.Conv2d):
+    """Atrous 3x3 conv (stride 1, padding = dilation >= 2, no bias) routed to
+    the in-tree MFMA kernels.
+
+    A subclass of nn.Conv2d so that parameter names, shapes, the default
+    initialisation and the RNG draw order are exactly those of the
+    ``nn.Conv2d(cin, cout, 3, padding=d, dilation=d, bias=False)`` it stands
+    in for. Backend select via TFOS_ATROUS: 'auto' (default: each of
+    forward, dgrad and the dead-tap collapse goes in-tree only where it was
+    measured no slower than the library), 'mfma' (in-tree, collapse
+    included), 'miopen' (library conv). When the dilation reaches the image
+    size only the centre tap is live and the conv runs as a 1x1 GEMM.
+    """
+
+    def __init__(self, in_channels, out_channels, dilation=2, device=None,
+                 dtype=None):
+        if int(dilation) < 2:
+            raise ValueError("DilatedConv3x3 needs dilation >= 2 "
+                             "(use Conv3x3 for an undilated conv)")
+        super().__init__(in_channels, out_channels, 3, stride=1,
+                         padding=int(dilation), dilation=int(dilation),
+                         bias=False, device=device, dtype=dtype)
+        self._eligible = in_channels % 32 == 0 and out_channels % 32 == 0 \
+            and out_channels >= 64
+
+    def forward(self, x):
+        if x.is_cuda and self._eligible and x.dtype == torch.bfloat16 \
+                and x.dim() == 4:
+            fd = self.dilation[0]
+            route = _atrous_route(x.shape[0], x.shape[2], x.shape[3],
+                                  self.in_channels, self.out_channels, fd)
+            if route is not None and get_ext(required=True) is not None:
+                x = x.contiguous(memory_format=torch.channels_last)
+                collapse, fwd_in_tree, dgrad_in_tree = route
+                if collapse:
+                    return _AtrousCollapsedFn.apply(x, self.weight)
+                return _AtrousConv3x3Fn.apply(x, self.weight, fd,
+                                              fwd_in_tree, dgrad_in_tree)
+        return super().forward(x)
+
+    def __prepare_scriptable__(self):
+        # the scripter must not compile the routed forward: hand it a plain
+        # conv that shares the weight and carries dilation and padding
+        _SCRIPT_CLONE_KEEPALIVE.append(self)
+        new = nn.Conv2d(self.in_channels, self.out_channels, 3, stride=1,
+                        padding=self.padding, dilation=self.dilation,
+                        bias=False)
+        new.weight = self.weight
+        new.train(self.training)
+        return new
+
+
 
 
 def _conv_parity_packed(x, packs, prefix, out, k, pp, accum=False):

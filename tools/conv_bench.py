@@ -4,6 +4,7 @@
 Covers the ResNet-50 stride-2 shapes and the U-Net decoder transposed convs
 (VERDICT r01 item 1/7). Run on a GPU box:
     python tools/conv_bench.py [--batch 1024]
+    python tools/conv_bench.py --atrous [--batch 32] [--rounds 9]
 """
 
 import argparse
@@ -55,9 +56,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--wrw", action="store_true")
+    ap.add_argument("--atrous", action="store_true",
+                    help="DeepLabV3 dilated 3x3 shapes, in-tree vs library")
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--json", default=None,
+                    help="also write the --atrous rows to this file")
     args = ap.parse_args()
     if args.wrw:
         bench_wrw(args.batch)
+        return
+    if args.atrous:
+        bench_atrous(32 if args.batch == 1024 else args.batch, args.rounds,
+                     args.iters, args.json)
         return
     from tensorflowonspark_amd.ops.modules import (Conv1x1, Conv3x3,
                                                    ConvTranspose2dMFMA)
@@ -129,6 +140,126 @@ def bench_wrw(batch=1024):
         print(f"wrw {k}x{k} s{s} {cin:5d}->{cout:5d} @{hw:3d}: "
               f"wrw2 {t2:7.3f} ms ({flops/t2/1e9:6.1f} TF) vs "
               f"MIOpen {tm:7.3f} ms ({flops/tm/1e9:6.1f} TF)")
+
+
+# DeepLabV3 @512^2 (output stride 16 -> 32x32 feature map):
+# (Cin, Cout, HW, dilation): stage-4 conv2, then the three ASPP branches
+ATROUS_SHAPES = [(512, 512, 32, 2), (2048, 256, 32, 12), (2048, 256, 32, 24),
+                 (2048, 256, 32, 36)]
+
+
+def ab_median(sides, rounds, iters):
+    """Median ms per call of each side. The sides alternate inside every
+    round (one process, one device), each timed with device events around
+    ``iters`` back-to-back calls, after a warm-up of every side."""
+    for fn in sides.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in sides}
+    for _ in range(rounds):
+        for k, fn in sides.items():
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) / iters)
+    return {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+
+
+def bench_atrous(batch=32, rounds=9, iters=5, json_path=None):
+    """Forward, dgrad and wrw of the DeepLabV3 atrous 3x3 convs, each timed
+    separately: the in-tree MFMA kernels (with and without the per-step
+    weight re-layout the module does from its fp32 parameter) against the
+    library conv. The rate-36 shape also times the dead-tap collapse (a 1x1
+    GEMM on the centre tap) against the library's 9-tap run."""
+    import json
+    import torch.nn.functional as F
+    from tensorflowonspark_amd.ops import get_ext
+    from tensorflowonspark_amd.ops.modules import live_taps
+    ext = get_ext(required=True)
+    conv_bwd = torch.ops.aten.convolution_backward
+    bf16 = torch.bfloat16
+    rows = []
+    torch.manual_seed(0)
+    for cin, cout, hw, fd in ATROUS_SHAPES:
+        N = batch
+        x = (torch.randn(N, cin, hw, hw, device="cuda") / 4).to(bf16) \
+            .contiguous(memory_format=torch.channels_last)
+        dy = (torch.randn(N, cout, hw, hw, device="cuda") / 4).to(bf16) \
+            .contiguous(memory_format=torch.channels_last)
+        w32 = torch.randn(cout, cin, 3, 3, device="cuda") / 16   # fp32 master
+        w4 = w32.to(bf16).contiguous(memory_format=torch.channels_last)
+
+        def w9_of():
+            return w32.permute(0, 2, 3, 1).reshape(cout, 9 * cin).to(bf16) \
+                .contiguous()
+
+        def wperm_of():
+            return w32.flip(2, 3).permute(1, 2, 3, 0).to(bf16).contiguous() \
+                .reshape(cin, 9 * cout)
+        w9, wperm = w9_of(), wperm_of()
+        flops = 2.0 * N * hw * hw * cout * 9 * cin
+
+        def lib_bwd(mask):
+            return lambda: conv_bwd(dy, x, w4, None, [1, 1], [fd, fd],
+                                    [fd, fd], False, [0, 0], 1, mask)
+        plan = {
+            "fwd": {
+                "mfma": lambda: ext.conv_mfma(x, w9, cout, 3, 3, 1, fd, 1,
+                                              -1, -1, fd=fd),
+                "mfma+prep": lambda: ext.conv_mfma(x, w9_of(), cout, 3, 3, 1,
+                                                   fd, 1, -1, -1, fd=fd),
+                "lib": lambda: F.conv2d(x, w4, None, 1, fd, fd),
+                "lib+cast": lambda: F.conv2d(x, w32.to(bf16), None, 1, fd,
+                                             fd),
+            },
+            "dgrad": {
+                "mfma": lambda: ext.conv_mfma(dy, wperm, cin, 3, 3, 1, fd, 1,
+                                              hw, hw, fd=fd),
+                "mfma+prep": lambda: ext.conv_mfma(dy, wperm_of(), cin, 3, 3,
+                                                   1, fd, 1, hw, hw, fd=fd),
+                "lib": lib_bwd([True, False, False]),
+            },
+            "wrw": {
+                "mfma": lambda: ext.conv_wrw2(dy, x, 3, 3, 1, fd, fd=fd),
+                "lib": lib_bwd([False, True, False]),
+            },
+        }
+        if live_taps(hw, hw, 3, 1, fd, fd) == ((1,), (1,)):
+            x2d = x.permute(0, 2, 3, 1).reshape(-1, cin)
+            dy2d = dy.permute(0, 2, 3, 1).reshape(-1, cout)
+            wc = w4[:, :, 1, 1].contiguous()
+            wct = wc.t().contiguous()
+            wc4 = wc.view(cout, cin, 1, 1)
+            plan["fwd"]["collapse"] = lambda: ext.gemm_bt(x2d, wc, True)
+            plan["fwd"]["collapse+prep"] = lambda: ext.gemm_bt(
+                x2d, w32[:, :, 1, 1].to(bf16).contiguous(), True)
+            plan["dgrad"]["collapse"] = lambda: ext.gemm_bt(dy2d, wct, True)
+            plan["dgrad"]["collapse+prep"] = lambda: ext.gemm_bt(
+                dy2d, w32[:, :, 1, 1].to(bf16).t().contiguous(), True)
+            plan["wrw"]["collapse-wrw2"] = lambda: ext.conv_wrw2(
+                dy, x, 1, 1, 1, 0)
+            plan["wrw"]["collapse-lib1x1"] = lambda: conv_bwd(
+                dy, x, wc4, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                [False, True, False])
+        for direction, sides in plan.items():
+            med = ab_median(sides, rounds, iters)
+            tag = "{:5s} {}->{} @{} d{} b{}".format(direction, cin, cout, hw,
+                                                     fd, N)
+            cells = "  ".join("{} {:.3f} ms ({:.0f} TF/s)".format(
+                k, v, flops / v / 1e9) for k, v in med.items())
+            print(tag + ": " + cells, flush=True)
+            rows.append(dict(direction=direction, cin=cin, cout=cout, hw=hw,
+                             fd=fd, batch=N, flops=flops, ms=med))
+    if json_path:
+        os.makedirs(os.path.dirname(os.path.abspath(json_path)),
+                    exist_ok=True)
+        with open(json_path, "w") as f:
+            json.dump(rows, f, indent=1)
 
 
 if __name__ == "__main__":
