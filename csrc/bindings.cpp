@@ -7,6 +7,21 @@
 
 extern "C" {
 int tfosr_bn_fast_blocks(long, int, int, int);
+void tfosr_bn_apply_dual(const void*, const void*, void*, unsigned char*,
+                         const float*, const float*, const float*, const float*,
+                         const float*, const float*, const float*, const float*,
+                         int, long, int, hipStream_t);
+void tfosr_bn_bwd_stats_dual(const void*, const void*, const void*,
+                             const unsigned char*, const float*, const float*,
+                             const float*, const float*, float*, int, int, long,
+                             int, hipStream_t);
+void tfosr_bn_bwd_merge_dual(const float*, int, float*, float*, float*, float*,
+                             int, hipStream_t);
+void tfosr_bn_bwd_dx_dual(const void*, const void*, const void*,
+                          const unsigned char*, void*, void*, const float*,
+                          const float*, const float*, const float*, const float*,
+                          const float*, const float*, const float*, const float*,
+                          int, long, int, hipStream_t);
 void tfosr_bn_stats(const void*, int, int, float*, int, int, int, long, hipStream_t);
 void tfosr_bn_finalize(const float*, int, const void*, int, int, long,
                        float*, float*, float*, float*,
@@ -269,6 +284,174 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y,
                   w.data_ptr<float>(), dg.data_ptr<float>(), db.data_ptr<float>(),
                   dx.data_ptr(), bf, l.nhwc, relu, total, l.C, l.HW, s);
   return {dx, dg, db};
+}
+
+// The join of two training-mode BatchNorms, y = relu(bn_a(xa) + bn_b(xb)), on
+// the NHWC fast path: the tail of a residual block with a downsample branch.
+// bn_dual_eligible() says whether the dual entries take a pair; callers fall
+// back to bn_fwd_train(xb) + bn_fwd_train(xa, res) and two bn_bwd otherwise.
+bool bn_dual_eligible(const at::Tensor& xa, const at::Tensor& xb) {
+  if (!xa.is_cuda() || !xb.is_cuda() || xa.dim() != 4) return false;
+  if (xa.scalar_type() != at::kBFloat16 && xa.scalar_type() != at::kFloat)
+    return false;
+  if (xb.scalar_type() != xa.scalar_type() || xb.device() != xa.device() ||
+      xb.sizes() != xa.sizes())
+    return false;
+  if (!xa.is_contiguous(at::MemoryFormat::ChannelsLast) ||
+      !xb.is_contiguous(at::MemoryFormat::ChannelsLast))
+    return false;
+  return tfosr_bn_fast_blocks(xa.numel(), (int)xa.size(1),
+                              xa.scalar_type() == at::kBFloat16, 1) > 0;
+}
+
+// -> {y, mean_a, rstd_a, mean_b, rstd_b, mask}; both running-stat pairs are
+// updated. The statistics are those of bn_fwd_train (same kernels).
+std::vector<at::Tensor> bn_dual_fwd_train(
+    at::Tensor xa, at::Tensor xb, at::Tensor w_a, at::Tensor b_a,
+    at::Tensor rm_a, at::Tensor rv_a, at::Tensor w_b, at::Tensor b_b,
+    at::Tensor rm_b, at::Tensor rv_b, double momentum, double eps) {
+  TORCH_CHECK(bn_dual_eligible(xa, xb),
+              "bn_dual: needs two same-shape channels_last GPU tensors on the "
+              "NHWC fast path");
+  auto l = bn_layout(xa);
+  int bf = dtype_flag(xa);
+  const at::Tensor* vecs[] = {&w_a, &b_a, &rm_a, &rv_a, &w_b, &b_b, &rm_b, &rv_b};
+  for (auto* t : vecs) bn_check_channel_vec(*t, xa, l.C, "per-channel vector");
+  auto opts = xa.options().dtype(at::kFloat);
+  long M = (long)l.N * l.HW;
+  long total = M * l.C;
+  int nb = tfosr_bn_fast_blocks(total, l.C, bf, 1);
+  auto ws = at::empty({(long)nb * 2 * l.C}, opts);
+  auto mean_a = at::empty({l.C}, opts), rstd_a = at::empty({l.C}, opts);
+  auto mean_b = at::empty({l.C}, opts), rstd_b = at::empty({l.C}, opts);
+  auto y = at::empty_like(xa);
+  auto mask = at::empty({total / (bf ? 8 : 4)}, xa.options().dtype(at::kByte));
+  auto s = cur_stream();
+  auto f = [](at::Tensor& t) { return t.data_ptr<float>(); };
+  // stream order lets the two statistics passes share one workspace
+  tfosr_bn_stats(xa.data_ptr(), bf, 1, f(ws), nb, l.N, l.C, l.HW, s);
+  tfosr_bn_finalize(f(ws), nb, xa.data_ptr(), bf, 1, l.HW, f(mean_a), f(rstd_a),
+                    f(rm_a), f(rv_a), M, l.C, (float)momentum, (float)eps, s);
+  tfosr_bn_stats(xb.data_ptr(), bf, 1, f(ws), nb, l.N, l.C, l.HW, s);
+  tfosr_bn_finalize(f(ws), nb, xb.data_ptr(), bf, 1, l.HW, f(mean_b), f(rstd_b),
+                    f(rm_b), f(rv_b), M, l.C, (float)momentum, (float)eps, s);
+  tfosr_bn_apply_dual(xa.data_ptr(), xb.data_ptr(), y.data_ptr(),
+                      mask.data_ptr<unsigned char>(), f(mean_a), f(rstd_a),
+                      f(w_a), f(b_a), f(mean_b), f(rstd_b), f(w_b), f(b_b), bf,
+                      total, l.C, s);
+  return {y, mean_a, rstd_a, mean_b, rstd_b, mask};
+}
+
+// -> {dxa, dxb, dgamma_a, dgamma_b, dbeta_a, dbeta_b}; the two dbeta are the
+// same sum (both BNs see the gated dy) in tensors of their own
+std::vector<at::Tensor> bn_dual_bwd(at::Tensor xa, at::Tensor xb, at::Tensor dy,
+                                    at::Tensor mask, at::Tensor w_a,
+                                    at::Tensor mean_a, at::Tensor rstd_a,
+                                    at::Tensor w_b, at::Tensor mean_b,
+                                    at::Tensor rstd_b) {
+  TORCH_CHECK(bn_dual_eligible(xa, xb),
+              "bn_dual: needs two same-shape channels_last GPU tensors on the "
+              "NHWC fast path");
+  auto l = bn_layout(xa);
+  int bf = dtype_flag(xa);
+  bn_check_like(dy, xa, true, false, "dy");
+  dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
+  const at::Tensor* vecs[] = {&w_a, &mean_a, &rstd_a, &w_b, &mean_b, &rstd_b};
+  for (auto* t : vecs) bn_check_channel_vec(*t, xa, l.C, "per-channel vector");
+  long total = (long)l.N * l.HW * l.C;
+  TORCH_CHECK(mask.device() == xa.device() && mask.scalar_type() == at::kByte &&
+                  mask.is_contiguous() && mask.numel() == total / (bf ? 8 : 4),
+              "bn_dual: mask must be the contiguous uint8 bitmask "
+              "bn_dual_fwd_train returned for these inputs");
+  auto opts = xa.options().dtype(at::kFloat);
+  int nb = tfosr_bn_fast_blocks(total, l.C, bf, 1);
+  auto ws = at::empty({(long)nb * 3 * l.C}, opts);
+  auto dg_a = at::empty({l.C}, opts), dg_b = at::empty({l.C}, opts);
+  auto db_a = at::empty({l.C}, opts), db_b = at::empty({l.C}, opts);
+  auto dxa = at::empty_like(xa), dxb = at::empty_like(xb);
+  auto s = cur_stream();
+  auto f = [](at::Tensor& t) { return t.data_ptr<float>(); };
+  const unsigned char* mask_ptr = mask.data_ptr<unsigned char>();
+  tfosr_bn_bwd_stats_dual(xa.data_ptr(), xb.data_ptr(), dy.data_ptr(), mask_ptr,
+                          f(mean_a), f(rstd_a), f(mean_b), f(rstd_b), f(ws), nb,
+                          bf, total, l.C, s);
+  tfosr_bn_bwd_merge_dual(f(ws), nb, f(dg_a), f(dg_b), f(db_a), f(db_b), l.C, s);
+  tfosr_bn_bwd_dx_dual(xa.data_ptr(), xb.data_ptr(), dy.data_ptr(), mask_ptr,
+                       dxa.data_ptr(), dxb.data_ptr(), f(mean_a), f(rstd_a),
+                       f(w_a), f(dg_a), f(mean_b), f(rstd_b), f(w_b), f(dg_b),
+                       f(db_a), bf, total, l.C, s);
+  return {dxa, dxb, dg_a, dg_b, db_a, db_b};
+}
+
+// One launch of one NHWC fast-path kernel family on caller-owned tensors, so
+// that tools/bn_bench.py can time stats, apply, bwd stats and bwd dx apart
+// (bn_fwd_train / bn_bwd run three launches each). family: 0 stats (x -> ws),
+// 1 apply (x, other = res or none -> out, mask), 2 bwd stats (x, other = dy,
+// mask -> ws, out = gout or none), 3 bwd dx (x, other = dy, mask -> out).
+// p0..p3 are per-channel fp32 vectors: mean, rstd, weight, bias for apply;
+// mean, rstd for bwd stats; mean, rstd, weight, dgamma for bwd dx with
+// dbeta in p4. ws holds bn_fast_blocks() * 2C floats.
+void bn_stage(int family, at::Tensor x, c10::optional<at::Tensor> other,
+              c10::optional<at::Tensor> out, c10::optional<at::Tensor> mask,
+              at::Tensor ws, std::vector<at::Tensor> p, bool relu) {
+  auto l = bn_layout(x);
+  int bf = dtype_flag(x);
+  long total = (long)l.N * l.HW * l.C;
+  int nb = tfosr_bn_fast_blocks(total, l.C, bf, l.nhwc);
+  TORCH_CHECK(nb > 0, "bn_stage: shape is not on the NHWC fast path");
+  const size_t need[4] = {0, 4, 2, 5};
+  TORCH_CHECK(family >= 0 && family < 4, "bn_stage: family must be 0..3");
+  TORCH_CHECK(p.size() == need[family], "bn_stage: family ", family, " takes ",
+              need[family], " per-channel vectors");
+  for (auto& t : p) bn_check_channel_vec(t, x, l.C, "per-channel vector");
+  TORCH_CHECK(ws.device() == x.device() && ws.scalar_type() == at::kFloat &&
+                  ws.is_contiguous() && ws.numel() >= (long)nb * 2 * l.C,
+              "bn_stage: ws must hold bn_fast_blocks() * 2C floats");
+  const void* other_ptr = nullptr;
+  if (other.has_value()) {
+    bn_check_like(*other, x, l.nhwc, true, "other");
+    other_ptr = other->data_ptr();
+  }
+  void* out_ptr = nullptr;
+  if (out.has_value()) {
+    bn_check_like(*out, x, l.nhwc, true, "out");
+    out_ptr = out->data_ptr();
+  }
+  unsigned char* mask_ptr = nullptr;
+  if (mask.has_value()) {
+    TORCH_CHECK(mask->device() == x.device() && mask->scalar_type() == at::kByte &&
+                    mask->is_contiguous() && mask->numel() == total / (bf ? 8 : 4),
+                "bn_stage: mask must be a contiguous uint8 tensor, one byte "
+                "per 16 B vector");
+    mask_ptr = mask->data_ptr<unsigned char>();
+  }
+  if (family != 0 && family != 1)
+    TORCH_CHECK(other_ptr != nullptr, "bn_stage: dy is required");
+  if (family == 1 || family == 3)
+    TORCH_CHECK(out_ptr != nullptr, "bn_stage: out is required");
+  if (family >= 2)
+    TORCH_CHECK(!relu || mask_ptr != nullptr, "bn_stage: relu needs the mask");
+  auto f = [&](size_t i) { return p[i].data_ptr<float>(); };
+  auto s = cur_stream();
+  switch (family) {
+    case 0:
+      tfosr_bn_stats(x.data_ptr(), bf, 1, ws.data_ptr<float>(), nb, l.N, l.C,
+                     l.HW, s);
+      break;
+    case 1:
+      tfosr_bn_apply(x.data_ptr(), other_ptr, out_ptr, mask_ptr, f(0), f(1),
+                     f(2), f(3), bf, 1, relu, total, l.C, l.HW, s);
+      break;
+    case 2:
+      tfosr_bn_bwd_stats(x.data_ptr(), other_ptr, nullptr, mask_ptr, out_ptr,
+                         f(0), f(1), ws.data_ptr<float>(), nb, bf, 1, relu,
+                         l.N, l.C, l.HW, s);
+      break;
+    default:
+      tfosr_bn_bwd_dx(x.data_ptr(), other_ptr, nullptr, mask_ptr, f(0), f(1),
+                      f(2), f(3), f(4), out_ptr, bf, 1, relu, total, l.C, l.HW,
+                      s);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -539,6 +722,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_fwd_train", &bn_fwd_train);
   m.def("bn_fwd_eval", &bn_fwd_eval);
   m.def("bn_bwd", &bn_bwd);
+  m.def("bn_dual_eligible", &bn_dual_eligible);
+  m.def("bn_dual_fwd_train", &bn_dual_fwd_train);
+  m.def("bn_dual_bwd", &bn_dual_bwd);
+  // blocks of the fast-path reduction kernels for a shape (0 = generic path):
+  // tools/bn_bench.py counts the partials' bytes with it
+  m.def("bn_fast_blocks", [](long total, int C, bool bf16, bool nhwc) {
+    return tfosr_bn_fast_blocks(total, C, bf16, nhwc);
+  });
+  m.def("bn_stage", &bn_stage);
   m.def("softmax_xent_fwd", &softmax_xent_fwd);
   m.def("softmax_xent_bwd", &softmax_xent_bwd);
   m.def("xent_dense_fwd", &xent_dense_fwd, py::arg("logits"), py::arg("target"),

@@ -322,6 +322,188 @@ __global__ void bwd_dx_fast(const T* __restrict__ x, const T* __restrict__ dy,
 }
 
 // ---------------------------------------------------------------------------
+// The join of two BatchNorms, y = relu(bn_a(xa) + bn_b(xb)): the tail of a
+// residual block whose shortcut ends in a BN of its own (a: the main branch,
+// b: the downsample branch). As two calls, the normalized shortcut is written
+// and read back in forward, and in backward the gated gradient is written
+// once and read three times; here each of xa, xb, dy is read once per pass.
+// Same layout rules, channel slots and mask format as the kernels above.
+// ---------------------------------------------------------------------------
+
+template <typename T>
+__global__ void bn_apply_dual_fast(const T* __restrict__ xa,
+                                   const T* __restrict__ xb, T* __restrict__ y,
+                                   unsigned char* __restrict__ mask,
+                                   const float* __restrict__ mean_a,
+                                   const float* __restrict__ rstd_a,
+                                   const float* __restrict__ w_a,
+                                   const float* __restrict__ b_a,
+                                   const float* __restrict__ mean_b,
+                                   const float* __restrict__ rstd_b,
+                                   const float* __restrict__ w_b,
+                                   const float* __restrict__ b_b,
+                                   u32 nvec, u32 C) {
+  constexpr int V = VecIO<T>::V;
+  const u32 c0 = channel_slot<V>(C);
+  float sca[V], mua[V], sha[V], scb[V], mub[V], shb[V], va[V], vb[V];
+  #pragma unroll
+  for (int j = 0; j < V; ++j) {
+    sca[j] = w_a[c0 + j] * rstd_a[c0 + j];
+    mua[j] = mean_a[c0 + j];
+    sha[j] = b_a[c0 + j];
+    scb[j] = w_b[c0 + j] * rstd_b[c0 + j];
+    mub[j] = mean_b[c0 + j];
+    shb[j] = b_b[c0 + j];
+  }
+  const u32 stride = gridDim.x * blockDim.x;
+  for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    VecIO<T>::load(xa + (size_t)i * V, va);
+    VecIO<T>::load(xb + (size_t)i * V, vb);
+    unsigned char m = 0;
+    #pragma unroll
+    for (int j = 0; j < V; ++j) {
+      // each branch as bn_apply_fast computes it; the shortcut is not rounded
+      // to T before the add
+      float o = (va[j] - mua[j]) * sca[j] + sha[j];
+      o += (vb[j] - mub[j]) * scb[j] + shb[j];
+      if (o > 0.f) m |= (1u << j);
+      va[j] = fmaxf(o, 0.f);
+    }
+    VecIO<T>::store(y + (size_t)i * V, va);
+    mask[i] = m;
+  }
+}
+
+// g = dy gated by the mask; dgamma_a += g * xhat_a; dgamma_b += g * xhat_b;
+// dbeta += g (the same sum for both BNs): partials[block][3C]
+template <typename T>
+__global__ void bwd_stats_dual_fast(const T* __restrict__ xa,
+                                    const T* __restrict__ xb,
+                                    const T* __restrict__ dy,
+                                    const unsigned char* __restrict__ mask,
+                                    const float* __restrict__ mean_a,
+                                    const float* __restrict__ rstd_a,
+                                    const float* __restrict__ mean_b,
+                                    const float* __restrict__ rstd_b,
+                                    float* __restrict__ partials, u32 nvec,
+                                    u32 C) {
+  extern __shared__ float lds[];  // [3C]: dgamma_a, dgamma_b, dbeta
+  constexpr int V = VecIO<T>::V;
+  const u32 c0 = channel_slot<V>(C);
+  for (u32 i = threadIdx.x; i < 3 * C; i += blockDim.x) lds[i] = 0.f;
+  __syncthreads();
+  float sga[V], sgb[V], sb[V], av[V], bv[V], dv[V];
+  float mua[V], rsa[V], mub[V], rsb[V];
+  #pragma unroll
+  for (int j = 0; j < V; ++j) {
+    sga[j] = 0.f; sgb[j] = 0.f; sb[j] = 0.f;
+    mua[j] = mean_a[c0 + j]; rsa[j] = rstd_a[c0 + j];
+    mub[j] = mean_b[c0 + j]; rsb[j] = rstd_b[c0 + j];
+  }
+  const u32 stride = gridDim.x * blockDim.x;
+  for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    VecIO<T>::load(xa + (size_t)i * V, av);
+    VecIO<T>::load(xb + (size_t)i * V, bv);
+    VecIO<T>::load(dy + (size_t)i * V, dv);
+    unsigned char m = mask[i];
+    #pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float g = ((m >> j) & 1) ? dv[j] : 0.f;
+      sb[j] += g;
+      sga[j] += g * (av[j] - mua[j]) * rsa[j];
+      sgb[j] += g * (bv[j] - mub[j]) * rsb[j];
+    }
+  }
+  #pragma unroll
+  for (int j = 0; j < V; ++j) {
+    atomicAdd(&lds[c0 + j], sga[j]);
+    atomicAdd(&lds[C + c0 + j], sgb[j]);
+    atomicAdd(&lds[2 * C + c0 + j], sb[j]);
+  }
+  __syncthreads();
+  float* out = partials + (size_t)blockIdx.x * 3 * C;
+  for (u32 i = threadIdx.x; i < 3 * C; i += blockDim.x) out[i] = lds[i];
+}
+
+// the shared dbeta goes to both BNs' outputs
+__global__ void bwd_stats_dual_merge(const float* __restrict__ partials,
+                                     int nblocks, u32 C,
+                                     float* __restrict__ dg_a,
+                                     float* __restrict__ dg_b,
+                                     float* __restrict__ db_a,
+                                     float* __restrict__ db_b) {
+  __shared__ float scratch[8];
+  const u32 c = blockIdx.x;
+  float sa = 0.f, sg = 0.f, sb = 0.f;
+  for (int b = threadIdx.x; b < nblocks; b += blockDim.x) {
+    sa += partials[(size_t)b * 3 * C + c];
+    sg += partials[(size_t)b * 3 * C + C + c];
+    sb += partials[(size_t)b * 3 * C + 2 * C + c];
+  }
+  sa = block_sum<256>(sa, scratch);
+  __syncthreads();
+  sg = block_sum<256>(sg, scratch);
+  __syncthreads();
+  sb = block_sum<256>(sb, scratch);
+  if (threadIdx.x == 0) {
+    dg_a[c] = sa;
+    dg_b[c] = sg;
+    db_a[c] = sb;
+    db_b[c] = sb;
+  }
+}
+
+// dxa and dxb as bwd_dx_fast computes each, from one read of dy and the mask
+template <typename T>
+__global__ void bwd_dx_dual_fast(const T* __restrict__ xa,
+                                 const T* __restrict__ xb,
+                                 const T* __restrict__ dy,
+                                 const unsigned char* __restrict__ mask,
+                                 T* __restrict__ dxa, T* __restrict__ dxb,
+                                 const float* __restrict__ mean_a,
+                                 const float* __restrict__ rstd_a,
+                                 const float* __restrict__ w_a,
+                                 const float* __restrict__ dg_a,
+                                 const float* __restrict__ mean_b,
+                                 const float* __restrict__ rstd_b,
+                                 const float* __restrict__ w_b,
+                                 const float* __restrict__ dg_b,
+                                 const float* __restrict__ db,
+                                 u32 nvec, u32 C, float invM) {
+  constexpr int V = VecIO<T>::V;
+  const u32 c0 = channel_slot<V>(C);
+  float sca[V], mua[V], rsa[V], dga[V], scb[V], mub[V], rsb[V], dgb[V], dbm[V];
+  float av[V], bv[V], dv[V];
+  #pragma unroll
+  for (int j = 0; j < V; ++j) {
+    mua[j] = mean_a[c0 + j]; rsa[j] = rstd_a[c0 + j];
+    sca[j] = w_a[c0 + j] * rsa[j];
+    dga[j] = dg_a[c0 + j] * invM;
+    mub[j] = mean_b[c0 + j]; rsb[j] = rstd_b[c0 + j];
+    scb[j] = w_b[c0 + j] * rsb[j];
+    dgb[j] = dg_b[c0 + j] * invM;
+    dbm[j] = db[c0 + j] * invM;
+  }
+  const u32 stride = gridDim.x * blockDim.x;
+  for (u32 i = blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    VecIO<T>::load(xa + (size_t)i * V, av);
+    VecIO<T>::load(xb + (size_t)i * V, bv);
+    VecIO<T>::load(dy + (size_t)i * V, dv);
+    unsigned char m = mask[i];
+    #pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float g = ((m >> j) & 1) ? dv[j] : 0.f;
+      float xhat_a = (av[j] - mua[j]) * rsa[j];
+      float xhat_b = (bv[j] - mub[j]) * rsb[j];
+      av[j] = sca[j] * (g - dbm[j] - xhat_a * dga[j]);
+      bv[j] = scb[j] * (g - dbm[j] - xhat_b * dgb[j]);
+    }
+    VecIO<T>::store(dxa + (size_t)i * V, av);
+    VecIO<T>::store(dxb + (size_t)i * V, bv);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Generic fallbacks (any layout/shape): scalar, 64-bit safe
 // ---------------------------------------------------------------------------
 
@@ -653,6 +835,70 @@ void tfosr_bn_bwd_dx(const void* x, const void* dy, const void* y,
     else { if (relu) DX_GEN(float, false, true); else DX_GEN(float, false, false); }
   }
 #undef DX_GEN
+}
+
+// The dual (two-BN join) launchers: NHWC fast path only, nb from
+// tfosr_bn_fast_blocks() must be > 0; the partials hold nb * 3C floats.
+
+void tfosr_bn_apply_dual(const void* xa, const void* xb, void* y,
+                         unsigned char* mask, const float* mean_a,
+                         const float* rstd_a, const float* w_a,
+                         const float* b_a, const float* mean_b,
+                         const float* rstd_b, const float* w_b,
+                         const float* b_b, int is_bf16, long total, int C,
+                         hipStream_t s) {
+  int vec = is_bf16 ? 8 : 4;
+  u32 nvec = (u32)(total / vec);
+  int grid = fast_grid(nvec, grid_quantum(C, vec));
+#define APPLY_DUAL(T) \
+  hipLaunchKernelGGL((bn_apply_dual_fast<T>), dim3(grid), dim3(256), 0, s, \
+                     (const T*)xa, (const T*)xb, (T*)y, mask, mean_a, rstd_a, \
+                     w_a, b_a, mean_b, rstd_b, w_b, b_b, nvec, (u32)C)
+  if (is_bf16) APPLY_DUAL(bf16_t); else APPLY_DUAL(float);
+#undef APPLY_DUAL
+}
+
+void tfosr_bn_bwd_stats_dual(const void* xa, const void* xb, const void* dy,
+                             const unsigned char* mask, const float* mean_a,
+                             const float* rstd_a, const float* mean_b,
+                             const float* rstd_b, float* partials, int nb,
+                             int is_bf16, long total, int C, hipStream_t s) {
+  int vec = is_bf16 ? 8 : 4;
+  u32 nvec = (u32)(total / vec);
+  size_t lds = 3 * (size_t)C * sizeof(float);
+#define BS_DUAL(T) \
+  hipLaunchKernelGGL((bwd_stats_dual_fast<T>), dim3(nb), dim3(256), lds, s, \
+                     (const T*)xa, (const T*)xb, (const T*)dy, mask, mean_a, \
+                     rstd_a, mean_b, rstd_b, partials, nvec, (u32)C)
+  if (is_bf16) BS_DUAL(bf16_t); else BS_DUAL(float);
+#undef BS_DUAL
+}
+
+void tfosr_bn_bwd_merge_dual(const float* partials, int nb, float* dg_a,
+                             float* dg_b, float* db_a, float* db_b, int C,
+                             hipStream_t s) {
+  hipLaunchKernelGGL(bwd_stats_dual_merge, dim3(C), dim3(256), 0, s,
+                     partials, nb, (u32)C, dg_a, dg_b, db_a, db_b);
+}
+
+void tfosr_bn_bwd_dx_dual(const void* xa, const void* xb, const void* dy,
+                          const unsigned char* mask, void* dxa, void* dxb,
+                          const float* mean_a, const float* rstd_a,
+                          const float* w_a, const float* dg_a,
+                          const float* mean_b, const float* rstd_b,
+                          const float* w_b, const float* dg_b, const float* db,
+                          int is_bf16, long total, int C, hipStream_t s) {
+  const float invM = 1.f / (float)(total / C);
+  int vec = is_bf16 ? 8 : 4;
+  u32 nvec = (u32)(total / vec);
+  int grid = fast_grid(nvec, grid_quantum(C, vec));
+#define DX_DUAL(T) \
+  hipLaunchKernelGGL((bwd_dx_dual_fast<T>), dim3(grid), dim3(256), 0, s, \
+                     (const T*)xa, (const T*)xb, (const T*)dy, mask, (T*)dxa, \
+                     (T*)dxb, mean_a, rstd_a, w_a, dg_a, mean_b, rstd_b, w_b, \
+                     dg_b, db, nvec, (u32)C, invM)
+  if (is_bf16) DX_DUAL(bf16_t); else DX_DUAL(float);
+#undef DX_DUAL
 }
 
 }  // extern "C"

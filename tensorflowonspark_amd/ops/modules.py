@@ -1179,6 +1179,15 @@ class _BottleneckFn(torch.autograd.Function):
     Tensors bf16 channels_last; BN stats/params fp32. Training mode only;
     saved set (t*, a*, masks, stats) matches what the unfused composition
     saves, so peak memory is unchanged.
+
+    With a downsample branch the block ends in y = relu(bn3(t3) + bnd(td)).
+    The dual BN entries (bn_dual_fwd_train / bn_dual_bwd) compute that join
+    and its backward with one read of each stream per pass: the normalized
+    shortcut is never written, read back or saved, and the gated gradient is
+    not written out and re-read by the second BN. The shortcut is then not
+    rounded to bf16 before the add, so y can differ from the two-call
+    composition by a bf16 ulp. ``TFOS_BN_DUAL=off`` or an ineligible pair
+    (bn_dual_eligible) keeps the two-call composition.
     """
 
     @staticmethod
@@ -1222,20 +1231,31 @@ class _BottleneckFn(torch.autograd.Function):
                 td = as4d(ext.gemm_bt(as2d(x), wdb, True), H, W)
             else:
                 td = ext.conv_mfma(x, wdb, C3, 1, 1, stride, 0, 1, -1, -1)
-            idn, md, rd, _kd = ext.bn_fwd_train(td, None, gd, bd, rmd, rvd,
-                                                momentum, eps, False)
-            opt = [td, idn, md, rd]
+            import os
+            dual = os.environ.get("TFOS_BN_DUAL", "on") != "off" \
+                and ext.bn_dual_eligible(t3, td)
+            if dual:
+                # y = relu(bn3(t3) + bnd(td)) in one pass: the normalized
+                # shortcut is neither written nor saved
+                y, m3, r3, md, rd, k3 = ext.bn_dual_fwd_train(
+                    t3, td, g3, b3, rm3, rv3, gd, bd, rmd, rvd, momentum, eps)
+                opt = [td, md, rd]
+            else:
+                idn, md, rd, _kd = ext.bn_fwd_train(td, None, gd, bd, rmd,
+                                                    rvd, momentum, eps, False)
+                opt = [td, idn, md, rd]
         else:
-            idn = None
+            dual = False
+            idn = x
             opt = []
-        res = idn if idn is not None else x
-        y, m3, r3, k3 = ext.bn_fwd_train(t3, res, g3, b3, rm3, rv3,
-                                         momentum, eps, True)
+        if not dual:
+            y, m3, r3, k3 = ext.bn_fwd_train(t3, idn, g3, b3, rm3, rv3,
+                                             momentum, eps, True)
 
         ctx.save_for_backward(x, w1, g1, t1, a1, m1, r1, k1,
                               w2, g2, t2, a2, m2, r2, k2,
                               w3, g3, t3, m3, r3, k3, y, wd, gd, *opt)
-        ctx.meta = (stride, wd is not None)
+        ctx.meta = (stride, wd is not None, dual)
         ctx.packs = packs
         return y
 
@@ -1244,7 +1264,7 @@ class _BottleneckFn(torch.autograd.Function):
         ext = get_ext(required=True)
         (x, w1, g1, t1, a1, m1, r1, k1, w2, g2, t2, a2, m2, r2, k2,
          w3, g3, t3, m3, r3, k3, y, wd, gd, *opt) = ctx.saved_tensors
-        stride, has_down = ctx.meta
+        stride, has_down, dual = ctx.meta
         packs = ctx.packs
         N, Cin, H, W = x.shape
         C1, C2, C3 = w1.shape[0], w2.shape[0], w3.shape[0]
@@ -1264,8 +1284,14 @@ class _BottleneckFn(torch.autograd.Function):
 
         # block tail: bn3(+res+relu) backward -> dt3 plus the gated residual
         # gradient dres (doubles as the dx accumulation buffer below)
-        dt3, dg3, db3, dres = ext.bn_bwd(t3, dy, y, k3, g3, m3, r3,
-                                         True, True)
+        if dual:
+            # both BNs of the join from one read of dy: dres never exists
+            td, md, rd = opt
+            dt3, dtd, dg3, dgd, db3, dbd = ext.bn_dual_bwd(
+                t3, td, dy, k3, g3, m3, r3, gd, md, rd)
+        else:
+            dt3, dg3, db3, dres = ext.bn_bwd(t3, dy, y, k3, g3, m3, r3,
+                                             True, True)
         dt3 = cl(dt3)
 
         def lib_wrw(dyt, xt, w4, s_, p_):
@@ -1322,12 +1348,13 @@ class _BottleneckFn(torch.autograd.Function):
         w1bT = packs["w1bT"].reshape(Cin, C1) if packs is not None \
             else w1.view(C1, Cin).to(torch.bfloat16).t().contiguous()
         if has_down:
-            td, idn, md, rd = opt
-            # downsample path: bnd backward (no relu) then conv dgrad
-            dtd, dgd, dbd = ext.bn_bwd(td, dres, idn,
-                                       torch.empty(0, dtype=torch.uint8,
-                                                   device=td.device),
-                                       gd, md, rd, False, False)
+            if not dual:
+                td, idn, md, rd = opt
+                # downsample path: bnd backward (no relu) then conv dgrad
+                dtd, dgd, dbd = ext.bn_bwd(td, dres, idn,
+                                           torch.empty(0, dtype=torch.uint8,
+                                                       device=td.device),
+                                           gd, md, rd, False, False)
             dtd = cl(dtd)
             dwd = ext.conv_wrw2(dtd, x, 1, 1, stride, 0) \
                 .view(C3, Cin, 1, 1) if _use_wrw2(1, Cin, C3) \

@@ -1,76 +1,196 @@
 #!/usr/bin/env python3
-"""Per-shape BN kernel bandwidth microbenchmark (round-3 backlog item 1).
+"""Per-shape, per-kernel bandwidth of the NHWC fast-path BatchNorm kernels.
 
-The aggregate profile says the fused BN set moves ~150-170 GB/step in ~40 ms
-(~3.5-4 TB/s effective vs ~8 achievable). This tool measures each BN op
-(fwd-train stats+apply, bwd stats+dx) per ResNet-50 layer shape and prints
-achieved GB/s, so the slow (shape, kernel) pairs are identifiable exactly.
+The four kernel families of csrc/bn_relu.hip (stats, apply, bwd stats, bwd dx)
+are launched one at a time through ``bn_stage`` on preallocated tensors and
+timed with device events: per round, ``--iters`` back-to-back launches between
+two events; the figure reported is the median over ``--rounds`` rounds. The
+numerator of TB/s is the bytes the launch really moves: every activation
+stream it reads or writes, the mask bytes and the fp32 partials. Each shape
+starts with a ``(copy)`` row, a plain device copy of the same tensor (1 read +
+1 write), as the yardstick of what a streaming kernel reaches on the machine
+at hand.
 
     python tools/bn_bench.py --batch 1024
+    python tools/bn_bench.py --batch 1024 --ext parent=/path/to/tfosr_hip_ops_parent.so
+
+``--ext NAME=PATH`` (repeatable) loads further builds of the extension next to
+the in-tree one and alternates all of them inside every round, shape by shape,
+so that drift hits each build alike. Such a build needs a module name of its
+own, equal to its file name (compile bindings.cpp with
+``-DTORCH_EXTENSION_NAME=tfosr_hip_ops_parent`` for the example above), and
+``bn_stage``: for an older commit, compile its csrc/bn_relu.hip with this
+commit's csrc/bindings.cpp.
+
+The variants timed are the ones the ResNet-50 step runs most: stats; apply
+with ReLU (and with ReLU + residual, ``apply+res``); bwd stats with the mask
+(and writing the gated gradient, ``bwd stats+g``); bwd dx with the mask.
 """
 
 import argparse
+import importlib.util
 import os
+import statistics
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
+# ResNet-50 BN shapes (C, H=W)
+RESNET50 = [(64, 112), (64, 56), (256, 56), (128, 56), (128, 28),
+            (512, 28), (256, 28), (256, 14), (1024, 14), (512, 14),
+            (512, 7), (2048, 7)]
 
-def timeit(fn, iters=10, warmup=3):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
+KERNELS = ["stats", "apply", "apply+res", "bwd stats", "bwd stats+g", "bwd dx"]
+
+COPY_TBS = 6.3   # streaming-copy bandwidth of the part, TB/s
+
+
+def load_ext(path):
+    name = os.path.basename(path).split(".")[0]
+    if name == "tfosr_hip_ops":
+        raise SystemExit("{}: pybind11 hands back the module already loaded "
+                         "under a name; build the other extension as, say, "
+                         "tfosr_hip_ops_parent.so".format(path))
+    spec = importlib.util.spec_from_file_location(name, path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    if not hasattr(mod, "bn_stage"):
+        raise SystemExit("{}: no bn_stage; build it with this commit's "
+                         "csrc/bindings.cpp".format(path))
+    return mod
+
+
+def bytes_moved(kernel, numel, esize, nvec, nb, C):
+    """Bytes one launch reads plus writes."""
+    t = numel * esize
+    part = nb * 2 * C * 4
+    return {
+        "stats": t + part,
+        "apply": 2 * t + nvec,
+        "apply+res": 3 * t + nvec,
+        "bwd stats": 2 * t + nvec + part,
+        "bwd stats+g": 3 * t + nvec + part,
+        "bwd dx": 3 * t + nvec,
+    }[kernel]
+
+
+def make_calls(ext, t):
+    """kernel name -> zero-argument launch, for one extension build."""
+    x, res, dy, out, mask, ws = (t["x"], t["res"], t["dy"], t["out"],
+                                 t["mask"], t["ws"])
+    mean, rstd, w, b, dg, db = (t["mean"], t["rstd"], t["w"], t["b"],
+                                t["dg"], t["db"])
+    st = ext.bn_stage
+    return {
+        "stats": lambda: st(0, x, None, None, None, ws, [], False),
+        "apply": lambda: st(1, x, None, out, mask, ws, [mean, rstd, w, b],
+                            True),
+        "apply+res": lambda: st(1, x, res, out, mask, ws, [mean, rstd, w, b],
+                                True),
+        "bwd stats": lambda: st(2, x, dy, None, mask, ws, [mean, rstd], True),
+        "bwd stats+g": lambda: st(2, x, dy, out, mask, ws, [mean, rstd],
+                                  True),
+        "bwd dx": lambda: st(3, x, dy, out, mask, ws, [mean, rstd, w, dg, db],
+                             True),
+    }
+
+
+def time_round(fn, iters):
+    a = torch.cuda.Event(enable_timing=True)
+    b = torch.cuda.Event(enable_timing=True)
+    a.record()
     for _ in range(iters):
         fn()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) / iters
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / iters   # ms
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--ext", action="append", default=[], metavar="NAME=PATH",
+                    help="another build of the extension to alternate with")
     args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bn_bench needs a GPU")
     from tensorflowonspark_amd.ops import get_ext
-    ext = get_ext(required=True)
+    exts = [("tree", get_ext(required=True))]
+    for spec in args.ext:
+        name, path = spec.split("=", 1)
+        exts.append((name, load_ext(path)))
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    esize, vec = (2, 8) if args.dtype == "bf16" else (4, 4)
     N = args.batch
-    # ResNet-50 BN shapes: (C, HW) with counts per step implicit
-    shapes = [(64, 112), (64, 56), (256, 56), (128, 56), (128, 28),
-              (512, 28), (256, 28), (256, 14), (1024, 14), (512, 14),
-              (512, 7), (2048, 7)]
-    eb = 2  # bf16
-    for C, HW in shapes:
-        x = torch.randn(N, C, HW, HW, device="cuda").to(torch.bfloat16) \
-            .contiguous(memory_format=torch.channels_last)
-        res = torch.randn_like(x)
-        dy = torch.randn_like(x)
-        g = torch.rand(C, device="cuda") + 0.5
-        b = torch.randn(C, device="cuda")
-        rm = torch.zeros(C, device="cuda")
-        rv = torch.ones(C, device="cuda")
-        nelem = x.numel()
-        tb = nelem * eb / 1e9  # GB per full tensor pass
+    dev = "cuda"
 
-        y, m, r, k = ext.bn_fwd_train(x, res, g, b, rm, rv, 0.1, 1e-5, True)
+    print("batch {} {}: ms and TB/s per launch, median of {} rounds x {} "
+          "launches".format(N, args.dtype, args.rounds, args.iters))
+    print("{:>5s} {:>4s} {:>7s} {:<12s}".format("C", "HW", "MB", "kernel")
+          + "".join(" {:>9s} ms {:>5s}TB/s {:>5s}".format(n[:9], "", "nb")
+                    for n, _ in exts))
+    total_ms = {n: 0.0 for n, _ in exts}
+    slow = []
+    for C, HW in RESNET50:
+        shape = (N, C, HW, HW)
 
-        t_stats = timeit(lambda: ext.bn_fwd_train(x, None, g, b, rm, rv,
-                                                  0.1, 1e-5, False))
-        t_full = timeit(lambda: ext.bn_fwd_train(x, res, g, b, rm, rv,
-                                                 0.1, 1e-5, True))
-        t_bwd = timeit(lambda: ext.bn_bwd(x, dy, y, k, g, m, r, True, True))
-        # traffic: fwd(no-res) = 2R+1W = 3 passes (+mask ~1/16);
-        # fwd(res+relu) = 3R+1W+mask; bwd(res) = stats 2R + gout 1W
-        #                + dx 2R+2W (dres) = 7 passes + mask reads
-        bw_f = 3 * tb / t_stats
-        bw_fr = 4.06 * tb / t_full
-        bw_b = 7.12 * tb / t_bwd
-        print(f"C={C:5d} HW={HW:4d} ({tb*1000:6.0f} MB/pass): "
-              f"fwd {t_stats*1e3:7.3f} ms {bw_f:6.0f} GB/s | "
-              f"fwd+res {t_full*1e3:7.3f} ms {bw_fr:6.0f} GB/s | "
-              f"bwd {t_bwd*1e3:7.3f} ms {bw_b:6.0f} GB/s")
+        def act():
+            return torch.randn(shape, device=dev).to(dtype).contiguous(
+                memory_format=torch.channels_last)
+
+        numel = N * C * HW * HW
+        nvec = numel // vec
+        t = {"x": act(), "res": act(), "dy": act(),
+             "out": torch.empty(shape, device=dev, dtype=dtype).contiguous(
+                 memory_format=torch.channels_last),
+             "mask": torch.randint(0, 256, (nvec,), device=dev,
+                                   dtype=torch.uint8),
+             "mean": torch.randn(C, device=dev),
+             "rstd": torch.rand(C, device=dev) + 0.5,
+             "w": torch.rand(C, device=dev) + 0.5,
+             "b": torch.randn(C, device=dev),
+             "dg": torch.randn(C, device=dev),
+             "db": torch.randn(C, device=dev)}
+        nbs = {n: e.bn_fast_blocks(numel, C, args.dtype == "bf16", True)
+               for n, e in exts}
+        t["ws"] = torch.empty(max(nbs.values()) * 2 * C, device=dev)
+        calls = {n: make_calls(e, t) for n, e in exts}
+        # yardstick on the same tensors: a plain device copy, 1 read + 1 write
+        copy = [time_round(lambda: t["out"].copy_(t["x"]), args.iters)
+                for _ in range(args.rounds + 1)][1:]
+        med = statistics.median(copy)
+        print("{:5d} {:4d} {:7.0f} {:<12s} {:12.4f} {:9.2f}".format(
+            C, HW, numel * esize / 1e6, "(copy)", med,
+            2 * numel * esize / med / 1e9), flush=True)
+        for k in KERNELS:
+            for n, _ in exts:          # warm up: code objects, caches
+                calls[n][k]()
+            torch.cuda.synchronize()
+            ms = {n: [] for n, _ in exts}
+            for _ in range(args.rounds):
+                for n, _ in exts:      # alternate the builds inside a round
+                    ms[n].append(time_round(calls[n][k], args.iters))
+            line = "{:5d} {:4d} {:7.0f} {:<12s}".format(
+                C, HW, numel * esize / 1e6, k)
+            for n, _ in exts:
+                med = statistics.median(ms[n])
+                tbs = bytes_moved(k, numel, esize, nvec, nbs[n], C) / med / 1e9
+                total_ms[n] += med
+                line += " {:12.4f} {:9.2f} {:5d}".format(med, tbs, nbs[n])
+                if n == "tree" and tbs < COPY_TBS * 2 / 3:
+                    slow.append((C, HW, k, tbs))
+            print(line, flush=True)
+        del t, calls
+    print("sum of medians, ms: " + ", ".join(
+        "{} {:.3f}".format(n, v) for n, v in total_ms.items()))
+    print("in-tree (shape, kernel) pairs under 2/3 of {} TB/s:".format(COPY_TBS))
+    for C, HW, k, tbs in slow:
+        print("  C={} HW={} {}: {:.2f} TB/s".format(C, HW, k, tbs))
 
 
 if __name__ == "__main__":
