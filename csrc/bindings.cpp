@@ -4,6 +4,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
+#include <climits>
 
 extern "C" {
 int tfosr_bn_fast_blocks(long, int, int, int);
@@ -643,8 +644,20 @@ at::Tensor nhwc_pack(at::Tensor x, at::Tensor mean, at::Tensor std_, double scal
                      bool out_bf16, bool channels_last) {
   TORCH_CHECK(x.dim() == 4 && x.scalar_type() == at::kByte && x.is_contiguous(),
               "nhwc_pack expects contiguous uint8 NHWC");
+  TORCH_CHECK(x.is_cuda(), "nhwc_pack: images must be on the GPU");
+  for (int d = 0; d < 4; ++d)
+    TORCH_CHECK(x.size(d) <= INT_MAX, "nhwc_pack: dimension ", d, " too large");
   int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   long HW = (long)H * W;
+  // the kernels index mean[c] / std_[c] for c < C through raw float pointers
+  auto check_stat = [&](const at::Tensor& t, const char* name) {
+    TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() &&
+                    t.device() == x.device() && t.numel() == C,
+                "nhwc_pack: ", name, " must be a contiguous fp32 tensor of C = ",
+                C, " elements on the images' device");
+  };
+  check_stat(mean, "mean");
+  check_stat(std_, "std");
   auto opts = x.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat);
   at::Tensor out;
   if (channels_last) {
@@ -658,10 +671,61 @@ at::Tensor nhwc_pack(at::Tensor x, at::Tensor mean, at::Tensor std_, double scal
   return out;
 }
 
+// The flat optimizer kernels walk raw float pointers over p.numel() elements
+// of every state tensor: all of them fp32, contiguous, equally long and on
+// p's GPU.
+void check_flat_state(const char* op, const at::Tensor& p,
+                      std::initializer_list<const at::Tensor*> others) {
+  TORCH_CHECK(p.is_cuda() && p.scalar_type() == at::kFloat && p.is_contiguous(),
+              op, " expects contiguous fp32 params on the GPU");
+  for (const at::Tensor* t : others)
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                    t->device() == p.device() && t->numel() == p.numel(),
+                op, ": every tensor must be contiguous fp32 with the params' ",
+                p.numel(), " elements on the params' device");
+}
+
+// Shared max-pool argument checks. The kernels index threads with u32 and
+// store the window tap in a u8; returns {OH, OW}.
+std::pair<long, long> check_pool_geometry(const char* op, const at::Tensor& t,
+                                          long C, long N, long H, long W,
+                                          long K, long S, long P) {
+  TORCH_CHECK(t.is_cuda(), op, " expects a GPU tensor");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat,
+              op, " expects bf16 or fp32");
+  const long V = t.scalar_type() == at::kBFloat16 ? 8 : 4;
+  TORCH_CHECK(C >= V && C % V == 0, op, ": C must be a multiple of ", V,
+              " for this dtype, got ", C);
+  TORCH_CHECK(K >= 1 && S >= 1 && K * K <= 256, op,
+              ": need K >= 1, S >= 1 and K*K <= 256 (the saved tap index is "
+              "one byte), got K=", K, " S=", S);
+  TORCH_CHECK(P >= 0 && P <= K / 2, op, ": need 0 <= P <= K/2, got P=", P);
+  TORCH_CHECK(N >= 0 && H >= 1 && W >= 1 && H <= INT_MAX && W <= INT_MAX &&
+              N <= INT_MAX && C <= INT_MAX && S <= INT_MAX,
+              op, ": empty or oversized dimension");
+  TORCH_CHECK(H + 2 * P >= K && W + 2 * P >= K, op,
+              ": the window does not fit the padded input");
+  const long OH = (H + 2 * P - K) / S + 1, OW = (W + 2 * P - K) / S + 1;
+  // one thread per V channels of a pixel, u32 index advanced by grid-stride:
+  // keep count + stride below 2^32 (no overflow in the products: each
+  // factor is below 2^31 and the running product is checked as it grows)
+  const long limit = 0xFFFFFFFFL - 2048L * 256L;
+  auto fits = [&](long h, long w) {
+    long n = N;
+    for (long f : {h, w, C / V}) {
+      if (n > limit / f) return false;
+      n *= f;
+    }
+    return true;
+  };
+  TORCH_CHECK(fits(H, W) && fits(OH, OW), op,
+              ": tensor too large for the kernels' 32-bit thread index");
+  return {OH, OW};
+}
+
 void sgd_step(at::Tensor p, at::Tensor g, at::Tensor m, double lr, double mu,
               double wd, bool nesterov) {
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous());
-  TORCH_CHECK(p.scalar_type() == at::kFloat, "sgd_step expects fp32 params");
+  check_flat_state("sgd_step", p, {&g, &m});
   tfosr_sgd_step(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
                  (float)lr, (float)mu, (float)wd, nesterov, p.numel(),
                  cur_stream());
@@ -745,7 +809,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam_step", [](at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                         double lr, double b1, double b2, double eps, double wd,
                         long step, bool decoupled) {
-    TORCH_CHECK(p.scalar_type() == at::kFloat);
+    check_flat_state("adam_step", p, {&g, &m, &v});
+    TORCH_CHECK(step >= 1 && step <= INT_MAX,
+                "adam_step: step counts from 1, got ", step);
     tfosr_adam_step(p.data_ptr<float>(), g.data_ptr<float>(),
                     m.data_ptr<float>(), v.data_ptr<float>(), lr, b1, b2, eps,
                     wd, (int)step, decoupled, p.numel(), cur_stream());
@@ -756,9 +822,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool_fwd", [](at::Tensor x, long K, long S, long P) {
     TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
                 "maxpool_fwd expects channels_last");
+    auto ohw = check_pool_geometry("maxpool_fwd", x, x.size(1), x.size(0),
+                                   x.size(2), x.size(3), K, S, P);
     int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-    int OH = (H + 2 * P - K) / S + 1, OW = (W + 2 * P - K) / S + 1;
-    TORCH_CHECK(C % (x.scalar_type() == at::kBFloat16 ? 8 : 4) == 0);
+    int OH = (int)ohw.first, OW = (int)ohw.second;
     auto y = at::empty({N, C, OH, OW}, x.options(),
                        at::MemoryFormat::ChannelsLast);
     auto idx = at::empty({N, OH, OW, C}, x.options().dtype(at::kByte));
@@ -934,8 +1001,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // per-step weight transform into the bf16 arena
   m.def("pack_bf16", [](at::Tensor descs, at::Tensor cum, long ndesc,
                         at::Tensor arena, long total) {
-    TORCH_CHECK(descs.is_cuda() && cum.is_cuda() && arena.is_cuda());
-    TORCH_CHECK(arena.scalar_type() == at::kBFloat16);
+    TORCH_CHECK(descs.is_cuda() && cum.is_cuda() && arena.is_cuda() &&
+                    descs.device() == arena.device() &&
+                    cum.device() == arena.device(),
+                "pack_bf16 expects descs, cum and arena on one GPU");
+    TORCH_CHECK(arena.scalar_type() == at::kBFloat16 && arena.is_contiguous(),
+                "pack_bf16 expects a contiguous bf16 arena");
+    TORCH_CHECK(ndesc >= 0 && ndesc <= INT_MAX, "pack_bf16: bad ndesc ", ndesc);
+    // 80 bytes = sizeof(PackDesc) in elementwise.hip
+    TORCH_CHECK(descs.scalar_type() == at::kByte && descs.is_contiguous() &&
+                    descs.numel() == ndesc * 80,
+                "pack_bf16: descs must hold ndesc * 80 contiguous bytes");
+    TORCH_CHECK(cum.scalar_type() == at::kLong && cum.is_contiguous() &&
+                    cum.numel() == ndesc + 1,
+                "pack_bf16: cum must hold ndesc + 1 contiguous int64");
+    TORCH_CHECK(total >= 0 && arena.numel() >= total,
+                "pack_bf16: arena holds ", arena.numel(), " elements, total is ",
+                total);
+    if (total == 0) return;
+    TORCH_CHECK(ndesc >= 1, "pack_bf16: no descriptor for ", total, " elements");
     tfosr_pack_bf16(descs.data_ptr(), cum.data_ptr(), (int)ndesc,
                     arena.data_ptr(), total, cur_stream());
   });
@@ -1027,6 +1111,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("maxpool_bwd", [](at::Tensor dy, at::Tensor idx, long H, long W,
                           long K, long S, long P) {
+    TORCH_CHECK(dy.dim() == 4, "maxpool_bwd expects a 4-D gradient");
+    auto ohw = check_pool_geometry("maxpool_bwd", dy, dy.size(1), dy.size(0),
+                                   H, W, K, S, P);
+    TORCH_CHECK(dy.size(2) == ohw.first && dy.size(3) == ohw.second,
+                "maxpool_bwd: a ", H, "x", W, " input pooled with K=", K,
+                " S=", S, " P=", P, " gives ", ohw.first, "x", ohw.second,
+                ", the gradient is ", dy.size(2), "x", dy.size(3));
+    TORCH_CHECK(idx.scalar_type() == at::kByte && idx.is_contiguous() &&
+                    idx.device() == dy.device() && idx.dim() == 4 &&
+                    idx.size(0) == dy.size(0) && idx.size(1) == dy.size(2) &&
+                    idx.size(2) == dy.size(3) && idx.size(3) == dy.size(1),
+                "maxpool_bwd: idx must be the contiguous uint8 (N, OH, OW, C) "
+                "tensor maxpool_fwd returned, on the gradient's device");
     dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
     int N = dy.size(0), C = dy.size(1), OH = dy.size(2), OW = dy.size(3);
     auto dx = at::empty({N, C, H, W}, dy.options(),

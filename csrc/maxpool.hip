@@ -49,7 +49,11 @@ __global__ void maxpool_fwd_nhwc(const T* __restrict__ x, T* __restrict__ y,
     float best[V];
     int bidx[V];
     #pragma unroll
-    for (int j = 0; j < V; ++j) { best[j] = -INFINITY; bidx[j] = 0; }
+    // bidx < 0: no in-bounds tap seen yet. The first one is always taken, so
+    // a window of -inf records a real pixel (never a padding tap) and its
+    // gradient has an owner; a NaN tap is taken too (v != v), so NaN
+    // propagates to y as in the library.
+    for (int j = 0; j < V; ++j) { best[j] = -INFINITY; bidx[j] = -1; }
     int ih0 = (int)oh * S - P, iw0 = (int)ow * S - P;
     for (int ky = 0; ky < K; ++ky) {
       int ih = ih0 + ky;
@@ -62,7 +66,10 @@ __global__ void maxpool_fwd_nhwc(const T* __restrict__ x, T* __restrict__ y,
         VecIO_load<T, V>(p, v);
         #pragma unroll
         for (int j = 0; j < V; ++j) {
-          if (v[j] > best[j]) { best[j] = v[j]; bidx[j] = ky * K + kx; }
+          if (bidx[j] < 0 || v[j] > best[j] || v[j] != v[j]) {
+            best[j] = v[j];
+            bidx[j] = ky * K + kx;
+          }
         }
       }
     }

@@ -289,11 +289,17 @@ def nhwc_pack(images_u8, mean=None, std=None, out_dtype=torch.bfloat16,
     if images_u8.is_cuda:
         ext = get_ext(required=True)
         if ext is not None:
+            dev = images_u8.device
             m = mean if mean is not None else torch.zeros(
-                images_u8.shape[-1], device=images_u8.device)
+                images_u8.shape[-1], device=dev)
             s = std if std is not None else torch.ones(
-                images_u8.shape[-1], device=images_u8.device)
-            return ext.nhwc_pack(images_u8.contiguous(), m.float(), s.float(),
+                images_u8.shape[-1], device=dev)
+            # the kernel reads C consecutive floats through a raw pointer
+            m = torch.as_tensor(m).to(device=dev, dtype=torch.float32) \
+                .contiguous()
+            s = torch.as_tensor(s).to(device=dev, dtype=torch.float32) \
+                .contiguous()
+            return ext.nhwc_pack(images_u8.contiguous(), m, s,
                                  float(scale), out_dtype == torch.bfloat16,
                                  channels_last)
     x = images_u8.to(torch.float32) * scale
