@@ -81,6 +81,16 @@ void tfosr_conv_par(const void*, const void*, const void*, void*, int, int,
                     int, int, int, int, int, int, int, unsigned long, int,
                     int, int, long, int, hipStream_t);
 void tfosr_pack_bf16(const void*, const void*, int, void*, long, hipStream_t);
+int tfosr_gemm_bt_stats_rows(int, int, int);
+void tfosr_gemm_bt_stats(const void*, const void*, void*, float*, int, int, int,
+                         hipStream_t);
+void tfosr_conv_mfma_stats(const void*, const void*, const void*, void*, float*,
+                           int, int, int, int, int, int, int, int, int, int, int,
+                           int, hipStream_t);
+int tfosr_bn_tile_ws_rows(int);
+void tfosr_bn_tile_finalize(const float*, int, int, float*, float*, float*,
+                            float*, float*, long, int, float, float,
+                            hipStream_t);
 }
 
 namespace tfosr {
@@ -339,6 +349,177 @@ std::vector<at::Tensor> bn_dual_fwd_train(
   tfosr_bn_apply_dual(xa.data_ptr(), xb.data_ptr(), y.data_ptr(),
                       mask.data_ptr<unsigned char>(), f(mean_a), f(rstd_a),
                       f(w_a), f(b_a), f(mean_b), f(rstd_b), f(w_b), f(b_b), bf,
+                      total, l.C, s);
+  return {y, mean_a, rstd_a, mean_b, rstd_b, mask};
+}
+
+// ---------------------------------------------------------------------------
+// Batch statistics from the GEMM / conv epilogues: gemm_bt_stats and
+// conv_mfma_stats return, next to the bf16 tensor, its per-tile partials
+// part[ceil(M / rows_per_tile)][2][C] (csrc/mfma_stats_epilogue.h); the _pre
+// entries below are bn_fwd_train / bn_dual_fwd_train with the statistics pass
+// over the tensor replaced by a merge of those partials.
+// ---------------------------------------------------------------------------
+
+// x must be what the fast NHWC kernels take, in bf16 (the partials are those
+// of a bf16 tensor); part must be the partials of a tensor of x's shape
+void bn_check_pre(const at::Tensor& x, const BNLayout& l, const at::Tensor& part,
+                  long rows_per_tile, const char* name) {
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && l.nhwc &&
+                  tfosr_bn_fast_blocks(x.numel(), l.C, 1, 1) > 0,
+              "bn_pre: needs a bfloat16 channels_last tensor on the NHWC fast "
+              "path");
+  TORCH_CHECK(part.device() == x.device(), "bn_pre: ", name, " must be on ",
+              x.device(), ", got ", part.device());
+  TORCH_CHECK(part.scalar_type() == at::kFloat, "bn_pre: ", name,
+              " must be float32");
+  TORCH_CHECK(part.is_contiguous(), "bn_pre: ", name, " must be contiguous");
+  TORCH_CHECK(rows_per_tile >= 16 && rows_per_tile <= 4096,
+              "bn_pre: bad rows_per_tile ", rows_per_tile);
+  const long M = (long)l.N * l.HW;
+  const long ntm = (M + rows_per_tile - 1) / rows_per_tile;
+  TORCH_CHECK(part.dim() == 3 && part.size(0) == ntm && part.size(1) == 2 &&
+                  part.size(2) == l.C,
+              "bn_pre: ", name, " must have shape [", ntm, ", 2, ", l.C,
+              "] for this input and rows_per_tile ", rows_per_tile);
+}
+
+void bn_tile_finalize(const at::Tensor& part, long rows_per_tile,
+                      const BNLayout& l, at::Tensor& mean, at::Tensor& rstd,
+                      at::Tensor& rm, at::Tensor& rv, double momentum,
+                      double eps, hipStream_t s) {
+  const int ntm = (int)part.size(0);
+  auto ws = at::empty({(long)tfosr_bn_tile_ws_rows(ntm) * 3 * l.C},
+                      part.options());
+  tfosr_bn_tile_finalize(part.data_ptr<float>(), ntm, (int)rows_per_tile,
+                         ws.data_ptr<float>(), mean.data_ptr<float>(),
+                         rstd.data_ptr<float>(), rm.data_ptr<float>(),
+                         rv.data_ptr<float>(), (long)l.N * l.HW, l.C,
+                         (float)momentum, (float)eps, s);
+}
+
+// the statistics pass over x and its merge, as bn_fwd_train launches them on
+// the NHWC fast path (nb = tfosr_bn_fast_blocks() > 0)
+void bn_stats_pass(const at::Tensor& x, int bf, const BNLayout& l,
+                   at::Tensor& mean, at::Tensor& rstd, at::Tensor& rm,
+                   at::Tensor& rv, double momentum, double eps, hipStream_t s) {
+  const long M = (long)l.N * l.HW;
+  const int nb = tfosr_bn_fast_blocks(M * l.C, l.C, bf, 1);
+  TORCH_CHECK(nb > 0, "bn: shape is not on the NHWC fast path");
+  auto ws = at::empty({(long)nb * 2 * l.C}, x.options().dtype(at::kFloat));
+  tfosr_bn_stats(x.data_ptr(), bf, 1, ws.data_ptr<float>(), nb, l.N, l.C, l.HW,
+                 s);
+  tfosr_bn_finalize(ws.data_ptr<float>(), nb, x.data_ptr(), bf, 1, l.HW,
+                    mean.data_ptr<float>(), rstd.data_ptr<float>(),
+                    rm.data_ptr<float>(), rv.data_ptr<float>(), M, l.C,
+                    (float)momentum, (float)eps, s);
+}
+
+// -> what bn_fwd_train returns. Launches: tile merge, finalize, apply.
+std::vector<at::Tensor> bn_fwd_train_pre(at::Tensor x,
+                                         c10::optional<at::Tensor> res,
+                                         at::Tensor part, long rows_per_tile,
+                                         at::Tensor w, at::Tensor b,
+                                         at::Tensor rm, at::Tensor rv,
+                                         double momentum, double eps,
+                                         bool relu) {
+  auto l = bn_layout(x);
+  dtype_flag(x);
+  bn_check_pre(x, l, part, rows_per_tile, "part");
+  const void* res_ptr = nullptr;
+  if (res.has_value()) {
+    bn_check_like(*res, x, true, true, "res");
+    res_ptr = res->data_ptr();
+  }
+  bn_check_channel_vec(w, x, l.C, "weight");
+  bn_check_channel_vec(b, x, l.C, "bias");
+  bn_check_channel_vec(rm, x, l.C, "running_mean");
+  bn_check_channel_vec(rv, x, l.C, "running_var");
+  auto opts = x.options().dtype(at::kFloat);
+  long total = (long)l.N * l.HW * l.C;
+  auto save_mean = at::empty({l.C}, opts);
+  auto save_rstd = at::empty({l.C}, opts);
+  auto y = at::empty_like(x);
+  at::Tensor mask = at::empty({relu ? total / 8 : 0},
+                              x.options().dtype(at::kByte));
+  auto s = cur_stream();
+  bn_tile_finalize(part, rows_per_tile, l, save_mean, save_rstd, rm, rv,
+                   momentum, eps, s);
+  tfosr_bn_apply(x.data_ptr(), res_ptr, y.data_ptr(),
+                 relu ? mask.data_ptr<unsigned char>() : nullptr,
+                 save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),
+                 w.data_ptr<float>(), b.data_ptr<float>(), 1, 1, relu, total,
+                 l.C, l.HW, s);
+  return {y, save_mean, save_rstd, mask};
+}
+
+// The statistics step of bn_fwd_train (part None: the pass over x and its
+// merge) or of bn_fwd_train_pre (the tile merge) alone, without the apply:
+// tools/bn_bench.py --epilogue times the two routes with it. -> {mean, rstd}
+std::vector<at::Tensor> bn_batch_stats(at::Tensor x,
+                                       c10::optional<at::Tensor> part,
+                                       long rows_per_tile, at::Tensor rm,
+                                       at::Tensor rv, double momentum,
+                                       double eps) {
+  auto l = bn_layout(x);
+  int bf = dtype_flag(x);
+  bn_check_channel_vec(rm, x, l.C, "running_mean");
+  bn_check_channel_vec(rv, x, l.C, "running_var");
+  auto opts = x.options().dtype(at::kFloat);
+  auto mean = at::empty({l.C}, opts), rstd = at::empty({l.C}, opts);
+  auto s = cur_stream();
+  if (part.has_value()) {
+    bn_check_pre(x, l, *part, rows_per_tile, "part");
+    bn_tile_finalize(*part, rows_per_tile, l, mean, rstd, rm, rv, momentum,
+                     eps, s);
+    return {mean, rstd};
+  }
+  TORCH_CHECK(l.nhwc, "bn_batch_stats: expects a channels_last tensor");
+  bn_stats_pass(x, bf, l, mean, rstd, rm, rv, momentum, eps, s);
+  return {mean, rstd};
+}
+
+// -> what bn_dual_fwd_train returns. A branch given without partials (None:
+// its producer had no statistics epilogue) gets the statistics pass.
+std::vector<at::Tensor> bn_dual_fwd_train_pre(
+    at::Tensor xa, at::Tensor xb, c10::optional<at::Tensor> part_a,
+    long rows_a, c10::optional<at::Tensor> part_b, long rows_b,
+    at::Tensor w_a, at::Tensor b_a, at::Tensor rm_a, at::Tensor rv_a,
+    at::Tensor w_b, at::Tensor b_b, at::Tensor rm_b, at::Tensor rv_b,
+    double momentum, double eps) {
+  TORCH_CHECK(bn_dual_eligible(xa, xb),
+              "bn_dual: needs two same-shape channels_last GPU tensors on the "
+              "NHWC fast path");
+  auto l = bn_layout(xa);
+  TORCH_CHECK(xa.scalar_type() == at::kBFloat16,
+              "bn_pre: needs bfloat16 tensors");
+  if (part_a.has_value()) bn_check_pre(xa, l, *part_a, rows_a, "part_a");
+  if (part_b.has_value()) bn_check_pre(xb, l, *part_b, rows_b, "part_b");
+  const at::Tensor* vecs[] = {&w_a, &b_a, &rm_a, &rv_a, &w_b, &b_b, &rm_b, &rv_b};
+  for (auto* t : vecs) bn_check_channel_vec(*t, xa, l.C, "per-channel vector");
+  auto opts = xa.options().dtype(at::kFloat);
+  long M = (long)l.N * l.HW;
+  long total = M * l.C;
+  auto mean_a = at::empty({l.C}, opts), rstd_a = at::empty({l.C}, opts);
+  auto mean_b = at::empty({l.C}, opts), rstd_b = at::empty({l.C}, opts);
+  auto y = at::empty_like(xa);
+  auto mask = at::empty({total / 8}, xa.options().dtype(at::kByte));
+  auto s = cur_stream();
+  auto f = [](at::Tensor& t) { return t.data_ptr<float>(); };
+  auto stats = [&](at::Tensor& x, c10::optional<at::Tensor>& part, long rows,
+                   at::Tensor& mean, at::Tensor& rstd, at::Tensor& rm,
+                   at::Tensor& rv) {
+    if (part.has_value()) {
+      bn_tile_finalize(*part, rows, l, mean, rstd, rm, rv, momentum, eps, s);
+      return;
+    }
+    bn_stats_pass(x, 1, l, mean, rstd, rm, rv, momentum, eps, s);
+  };
+  stats(xa, part_a, rows_a, mean_a, rstd_a, rm_a, rv_a);
+  stats(xb, part_b, rows_b, mean_b, rstd_b, rm_b, rv_b);
+  tfosr_bn_apply_dual(xa.data_ptr(), xb.data_ptr(), y.data_ptr(),
+                      mask.data_ptr<unsigned char>(), f(mean_a), f(rstd_a),
+                      f(w_a), f(b_a), f(mean_b), f(rstd_b), f(w_b), f(b_b), 1,
                       total, l.C, s);
   return {y, mean_a, rstd_a, mean_b, rstd_b, mask};
 }
@@ -753,6 +934,37 @@ at::Tensor gemm_bt(at::Tensor a, at::Tensor b, bool out_bf16) {
   return out;
 }
 
+// -> (c, part, rows_per_tile): c is gemm_bt(a, b, out_bf16=True) bit for bit;
+// part[ceil(M / rows_per_tile)][2][N] are c's per-tile BatchNorm partials for
+// bn_fwd_train_pre, or None (rows_per_tile 0) where the dispatched kernel has
+// no statistics epilogue and the caller keeps the separate pass.
+py::tuple gemm_bt_stats(at::Tensor a, at::Tensor b) {
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(1),
+              "gemm_bt_stats: A[M,K], B[N,K]");
+  TORCH_CHECK(a.is_cuda(), "gemm_bt_stats: a must be a GPU tensor");
+  TORCH_CHECK(b.device() == a.device(), "gemm_bt_stats: b must be on ",
+              a.device());
+  TORCH_CHECK(a.scalar_type() == at::kBFloat16 &&
+                  b.scalar_type() == at::kBFloat16,
+              "gemm_bt_stats: a and b must be bfloat16");
+  const long M = a.size(0), N = b.size(0), K = a.size(1);
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && M <= INT_MAX && N <= INT_MAX &&
+                  K <= INT_MAX, "gemm_bt_stats: bad sizes");
+  const int rows = K % 32 == 0
+      ? tfosr_gemm_bt_stats_rows((int)M, (int)N, (int)K) : 0;
+  if (rows == 0)  // gemm_bt's own route (it also pads a ragged K)
+    return py::make_tuple(gemm_bt(a, b, true), py::none(), 0);
+  a = a.contiguous();
+  b = b.contiguous();
+  auto out = at::empty({M, N}, a.options());
+  auto part = at::empty({(M + rows - 1) / rows, 2, N},
+                        a.options().dtype(at::kFloat));
+  tfosr_gemm_bt_stats(a.data_ptr(), b.data_ptr(), out.data_ptr(),
+                      part.data_ptr<float>(), (int)M, (int)N, (int)K,
+                      cur_stream());
+  return py::make_tuple(out, part, rows);
+}
+
 at::Tensor gemm_bf16(at::Tensor a, at::Tensor b) {
   // A[M,K] @ B[K,N]: feed B^T (contiguous [N,K]) to the kernel
   return gemm_bt(a, b.t().contiguous(), /*out_bf16=*/false);
@@ -773,13 +985,72 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 6
+#define TFOSR_API_VERSION 7
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
 // tensor that fits the device, so a reach capped at 2^20 keeps every such
 // sum far inside the int range.
 static constexpr long kMaxTapReach = 1L << 20;
+
+// conv_mfma and conv_mfma_stats (see their m.def below). stats: also return
+// the output's BatchNorm tile partials [ceil(N*OH*OW / 256)][2][Cout] where
+// the launch has the statistics epilogue (input dilation 1, bf16 output).
+static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
+    at::Tensor x, at::Tensor wk, long Cout, long fh, long fw, long S, long P,
+    long D, long OH, long OW, long fd, bool out_f32, bool stats) {
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "conv_mfma expects channels_last input");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
+              wk.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(fh >= 1 && fw >= 1 && fh * fw <= 49, "bad filter dims");
+  TORCH_CHECK(D == 1 || D == 2, "input dilation must be 1 or 2");
+  TORCH_CHECK(fd >= 1, "conv_mfma: filter dilation fd must be >= 1, got ",
+              fd);
+  TORCH_CHECK(fd == 1 || D == 1,
+              "conv_mfma: filter dilation fd > 1 requires input dilation "
+              "D == 1");
+  // ih = oh*S - P + r*fd is computed in int: keep the tap reach far
+  // below 2^31 so it cannot overflow whatever the image size
+  TORCH_CHECK(fd <= kMaxTapReach && fd * (fh - 1) <= kMaxTapReach &&
+                  fd * (fw - 1) <= kMaxTapReach,
+              "conv_mfma: fd, fd*(fh-1) and fd*(fw-1) must be <= ",
+              kMaxTapReach);
+  long taps = fh * fw;
+  int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(Cin % 32 == 0, "conv_mfma requires Cin % 32 == 0");
+  TORCH_CHECK(wk.size(1) == taps * Cin);
+  if (OH < 0) {
+    long HV = (H - 1) * D + 1, WV = (W - 1) * D + 1;
+    long nh = HV + 2 * P - fd * (fh - 1) - 1;
+    long nw = WV + 2 * P - fd * (fw - 1) - 1;
+    TORCH_CHECK(nh >= 0 && nw >= 0,
+                "conv_mfma: the dilated filter does not fit the padded "
+                "input");
+    OH = nh / S + 1;
+    OW = nw / S + 1;
+  }
+  auto y = at::empty({N, Cout, OH, OW},
+                     x.options().dtype(out_f32 ? at::kFloat : at::kBFloat16),
+                     at::MemoryFormat::ChannelsLast);
+  auto guard = at::zeros({64}, x.options());
+  if (stats && D == 1 && !out_f32) {
+    TORCH_CHECK(x.is_cuda() && wk.device() == x.device(),
+                "conv_mfma_stats: x and wk must be on one GPU");
+    const long M = (long)N * OH * OW;
+    auto part = at::empty({(M + 255) / 256, 2, Cout},
+                          x.options().dtype(at::kFloat));
+    tfosr_conv_mfma_stats(x.data_ptr(), wk.contiguous().data_ptr(),
+                          guard.data_ptr(), y.data_ptr(),
+                          part.data_ptr<float>(), N, H, W, Cin, Cout, OH, OW, S,
+                          P, taps, fw, (int)fd, cur_stream());
+    return {y, part};
+  }
+  tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard.data_ptr(),
+                  y.data_ptr(), /*out_bf16=*/out_f32 ? 0 : 1, N, H, W, Cin,
+                  Cout, OH, OW, S, P, taps, fw, D, 0, (int)fd, cur_stream());
+  return {y, c10::nullopt};
+}
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("api_version", []() { return TFOSR_API_VERSION; });
@@ -865,48 +1136,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_mfma", [](at::Tensor x, at::Tensor wk, long Cout, long fh,
                         long fw, long S, long P, long D, long OH, long OW,
                         long fd, bool out_f32) {
-    TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv_mfma expects channels_last input");
-    TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-                wk.scalar_type() == at::kBFloat16);
-    TORCH_CHECK(fh >= 1 && fw >= 1 && fh * fw <= 49, "bad filter dims");
-    TORCH_CHECK(D == 1 || D == 2, "input dilation must be 1 or 2");
-    TORCH_CHECK(fd >= 1, "conv_mfma: filter dilation fd must be >= 1, got ",
-                fd);
-    TORCH_CHECK(fd == 1 || D == 1,
-                "conv_mfma: filter dilation fd > 1 requires input dilation "
-                "D == 1");
-    // ih = oh*S - P + r*fd is computed in int: keep the tap reach far
-    // below 2^31 so it cannot overflow whatever the image size
-    TORCH_CHECK(fd <= kMaxTapReach && fd * (fh - 1) <= kMaxTapReach &&
-                    fd * (fw - 1) <= kMaxTapReach,
-                "conv_mfma: fd, fd*(fh-1) and fd*(fw-1) must be <= ",
-                kMaxTapReach);
-    long taps = fh * fw;
-    int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-    TORCH_CHECK(Cin % 32 == 0, "conv_mfma requires Cin % 32 == 0");
-    TORCH_CHECK(wk.size(1) == taps * Cin);
-    if (OH < 0) {
-      long HV = (H - 1) * D + 1, WV = (W - 1) * D + 1;
-      long nh = HV + 2 * P - fd * (fh - 1) - 1;
-      long nw = WV + 2 * P - fd * (fw - 1) - 1;
-      TORCH_CHECK(nh >= 0 && nw >= 0,
-                  "conv_mfma: the dilated filter does not fit the padded "
-                  "input");
-      OH = nh / S + 1;
-      OW = nw / S + 1;
-    }
-    auto y = at::empty({N, Cout, OH, OW},
-                       x.options().dtype(out_f32 ? at::kFloat : at::kBFloat16),
-                       at::MemoryFormat::ChannelsLast);
-    auto guard = at::zeros({64}, x.options());
-    tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard.data_ptr(),
-                    y.data_ptr(), /*out_bf16=*/out_f32 ? 0 : 1, N, H, W, Cin,
-                    Cout, OH, OW, S, P, taps, fw, D, 0, (int)fd, cur_stream());
-    return y;
+    return conv_mfma_impl(x, wk, Cout, fh, fw, S, P, D, OH, OW, fd, out_f32,
+                          /*stats=*/false).first;
   }, py::arg("x"), py::arg("wk"), py::arg("Cout"), py::arg("fh"),
      py::arg("fw"), py::arg("S"), py::arg("P"), py::arg("D"), py::arg("OH"),
      py::arg("OW"), py::arg("fd") = 1, py::arg("out_f32") = false);
+  // -> (y, part, rows_per_tile): y is conv_mfma(...) bit for bit; part holds
+  // y's per-tile BatchNorm partials for bn_fwd_train_pre, or None
+  // (rows_per_tile 0) where the launch has no statistics epilogue (input
+  // dilation 2 or fp32 output) and the caller keeps the separate pass.
+  m.def("conv_mfma_stats", [](at::Tensor x, at::Tensor wk, long Cout, long fh,
+                              long fw, long S, long P, long D, long OH,
+                              long OW, long fd, bool out_f32) {
+    auto r = conv_mfma_impl(x, wk, Cout, fh, fw, S, P, D, OH, OW, fd, out_f32,
+                            /*stats=*/true);
+    if (!r.second.has_value()) return py::make_tuple(r.first, py::none(), 0);
+    return py::make_tuple(r.first, *r.second, 256);
+  }, py::arg("x"), py::arg("wk"), py::arg("Cout"), py::arg("fh"),
+     py::arg("fw"), py::arg("S"), py::arg("P"), py::arg("D"), py::arg("OH"),
+     py::arg("OW"), py::arg("fd") = 1, py::arg("out_f32") = false);
+  m.def("gemm_bt_stats", &gemm_bt_stats, py::arg("a"), py::arg("b"));
+  m.def("bn_fwd_train_pre", &bn_fwd_train_pre);
+  m.def("bn_dual_fwd_train_pre", &bn_dual_fwd_train_pre);
+  m.def("bn_batch_stats", &bn_batch_stats);
   // conv_mfma accumulating INTO an existing channels_last tensor:
   // out += conv(x, wk) — fuses the residual-join gradient accumulation the
   // eager autograd would do as a separate whole-tensor add (8.4 ms/step of

@@ -180,6 +180,106 @@ __global__ void stats_merge_finalize(const float* __restrict__ partials,
   }
 }
 
+// The same statistics from the tile partials that the GEMM / conv statistics
+// epilogues leave behind (mfma_stats_epilogue.h): part[ntm][2][C], row t =
+// (mean_t, M2_t) of the n_t = min(rows_per_tile, M - t * rows_per_tile) rows
+// of tile t. Tiles combine by the parallel-variance formula, taken around the
+// first tile's mean m0 so that the sums stay small where |mean| >> std:
+//
+//   mean = m0 + S1 / M,   S1 = sum n_t (mean_t - m0)
+//   var  = (sum M2_t + S2) / M - (S1 / M)^2,   S2 = sum n_t (mean_t - m0)^2
+//
+// There are up to ~25 k tile rows (ResNet-50 layer1 at batch 1024), 3 % of the
+// tensor's bytes, so the merge is two-level and reads coalesced over channels:
+// a block is 64 channels x 4 row lanes; level 1 gives block (cx, k) the rows
+// [k * chunk, (k + 1) * chunk) and writes ws[k][3][C] = (S1, S2, sum M2);
+// level 2 sums the <= 256 rows of ws the same way and finalizes. Every sum
+// has a fixed order.
+#define TFOSR_TILE_MERGE_ROWS 256  // most rows of ws (level-1 blocks per column)
+
+static inline int tile_merge_chunk(int ntm) {
+  int chunk = (ntm + TFOSR_TILE_MERGE_ROWS - 1) / TFOSR_TILE_MERGE_ROWS;
+  if (chunk < 32) chunk = 32;
+  return (chunk + 3) / 4 * 4;
+}
+
+// sum over the 4 row lanes of a 64 x 4 block; valid in the threads of lane 0
+__device__ __forceinline__ void tile_merge_lanes(float (&v)[3],
+                                                 float (*lds)[4][64], u32 tx,
+                                                 u32 ty) {
+  #pragma unroll
+  for (int j = 0; j < 3; ++j) lds[j][ty][tx] = v[j];
+  __syncthreads();
+  if (ty == 0) {
+    #pragma unroll
+    for (int j = 0; j < 3; ++j)
+      v[j] = (lds[j][0][tx] + lds[j][1][tx]) + (lds[j][2][tx] + lds[j][3][tx]);
+  }
+}
+
+__global__ void tile_stats_reduce(const float* __restrict__ part, int ntm, u32 C,
+                                  int rows_per_tile, long M, int chunk,
+                                  float* __restrict__ ws) {
+  __shared__ float lds[3][4][64];
+  const u32 tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const u32 c = blockIdx.x * 64 + tx;
+  const int r0 = blockIdx.y * chunk;
+  const int r1 = r0 + chunk < ntm ? r0 + chunk : ntm;
+  float v[3] = {0.f, 0.f, 0.f};
+  if (c < C) {
+    const float m0 = part[c];
+    for (int r = r0 + (int)ty; r < r1; r += 4) {
+      const float* p = part + (size_t)r * 2 * C;
+      const long rem = M - (long)r * rows_per_tile;
+      const float n = (float)(rem < rows_per_tile ? rem : rows_per_tile);
+      const float d = p[c] - m0;
+      v[0] += n * d;
+      v[1] += n * d * d;
+      v[2] += p[C + c];
+    }
+  }
+  tile_merge_lanes(v, lds, tx, ty);
+  if (ty == 0 && c < C) {
+    float* out = ws + (size_t)blockIdx.y * 3 * C;
+    out[c] = v[0];
+    out[C + c] = v[1];
+    out[2 * C + c] = v[2];
+  }
+}
+
+__global__ void tile_stats_finalize(const float* __restrict__ ws, int nrows,
+                                    u32 C, const float* __restrict__ part,
+                                    float* __restrict__ save_mean,
+                                    float* __restrict__ save_rstd,
+                                    float* __restrict__ running_mean,
+                                    float* __restrict__ running_var, long M,
+                                    float momentum, float eps) {
+  __shared__ float lds[3][4][64];
+  const u32 tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const u32 c = blockIdx.x * 64 + tx;
+  float v[3] = {0.f, 0.f, 0.f};
+  if (c < C) {
+    for (int r = (int)ty; r < nrows; r += 4) {
+      const float* p = ws + (size_t)r * 3 * C;
+      v[0] += p[c];
+      v[1] += p[C + c];
+      v[2] += p[2 * C + c];
+    }
+  }
+  tile_merge_lanes(v, lds, tx, ty);
+  if (ty != 0 || c >= C) return;
+  const float dmean = v[0] / (float)M;
+  const float var = fmaxf((v[2] + v[1]) / (float)M - dmean * dmean, 0.f);
+  const float mean = part[c] + dmean;
+  save_mean[c] = mean;
+  save_rstd[c] = rsqrtf(var + eps);
+  if (running_mean != nullptr) {
+    float unbiased = (M > 1) ? var * (float)M / (float)(M - 1) : var;
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+  }
+}
+
 // normalize (+add residual)(+relu); with RELU, also emit a per-element
 // sign bitmask (1 byte per vector) so backward never re-reads y for gating
 template <typename T, bool RELU, bool ADD>
@@ -703,6 +803,29 @@ void tfosr_bn_finalize(const float* partials, int nb, const void* x,
                      nb > 0 ? 1 : (int)(M < TFOSR_BN_SHIFT_PIXELS ? M : TFOSR_BN_SHIFT_PIXELS),
                      save_mean, save_rstd,
                      running_mean, running_var, M, momentum, eps);
+}
+
+// rows of the level-1 workspace tfosr_bn_tile_finalize() needs for ntm tile
+// rows: ws holds rows * 3C floats
+int tfosr_bn_tile_ws_rows(int ntm) {
+  const int chunk = tile_merge_chunk(ntm);
+  return (ntm + chunk - 1) / chunk;
+}
+
+// tfosr_bn_stats + tfosr_bn_finalize from the tile partials part[ntm][2][C] of
+// a GEMM / conv statistics epilogue instead of from the tensor
+void tfosr_bn_tile_finalize(const float* part, int ntm, int rows_per_tile,
+                            float* ws, float* save_mean, float* save_rstd,
+                            float* running_mean, float* running_var, long M,
+                            int C, float momentum, float eps, hipStream_t s) {
+  const int chunk = tile_merge_chunk(ntm);
+  const int nrows = (ntm + chunk - 1) / chunk;
+  const int cgroups = (C + 63) / 64;
+  hipLaunchKernelGGL(tile_stats_reduce, dim3(cgroups, nrows), dim3(256), 0, s,
+                     part, ntm, (u32)C, rows_per_tile, M, chunk, ws);
+  hipLaunchKernelGGL(tile_stats_finalize, dim3(cgroups), dim3(256), 0, s, ws,
+                     nrows, (u32)C, part, save_mean, save_rstd, running_mean,
+                     running_var, M, momentum, eps);
 }
 
 // relu: 0/1; res: nullptr for plain BN; mask: sign bits out (fast path only)

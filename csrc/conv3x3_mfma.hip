@@ -30,6 +30,8 @@
 // changes; out-of-image taps still redirect to the guard. Launches with
 // D == 2, PAR or ACC pass fd = 1.
 #include "tfosr_common.h"
+#include "mfma_stats_epilogue.h"
+#include <type_traits>
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -53,14 +55,22 @@ __device__ __forceinline__ void c3_stage16(const char* src,
 // rows exactly (the D=2 divisibility always holds), so none of the 4x
 // dilation-zero MFMA waste of the plain D=2 formulation remains. Stores
 // land at the class's strided pixels of the REAL output (OWr/total given).
+//
+// STATS (plain bf16 forward only: D == 1, no ACC, no PAR): after the tile
+// stores, the block also writes the tile's per-channel BatchNorm partial
+// (mean, M2) to row tile_m / BM of part[ceil(M / BM)][2][Cout] — see
+// mfma_stats_epilogue.h. The stores themselves are the non-STATS kernel's.
 template <typename OT, int WRG, int WCG, int MI, int D = 1, bool ACC = false,
-          bool PAR = false>
+          bool PAR = false, bool STATS = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ W9,
     const bf16_t* __restrict__ guard, OT* __restrict__ C,
     int Nn, int H, int Wd, int Cin, int Cout, int OH, int OW, int S, int P,
     int taps, int fw, int pixst, unsigned long tap_pack, int oh0, int ow0,
-    int OWr, long OHOWr, int fd) {
+    int OWr, long OHOWr, int fd, float* __restrict__ part) {
+  static_assert(!STATS || (D == 1 && !ACC && !PAR &&
+                           std::is_same<OT, bf16_t>::value),
+                "the statistics epilogue exists for the plain bf16 forward");
   constexpr int BM = WRG * MI * 16;
   constexpr int BN = WCG * 64;
   constexpr int ABYTES = BM * C3_BK * 2;
@@ -245,45 +255,58 @@ __global__ __launch_bounds__(512, 1) void conv3x3_kernel(
       }
     }
   }
+  if constexpr (STATS) {
+    static_assert(TFOSR_TILE_STATS_LDS_FLOATS(WRG, BN) * 4 <= sizeof(lds), "");
+    // nkt >= 1 (K >= Cin >= 32): the K loop's closing barrier has retired
+    // every read of the staging ring
+    mfma_tile_stats<MI, WRG, BN>(acc, (float*)lds, wr, wc, lane, t, tile_m,
+                                 tile_n, M, Cout,
+                                 part + (tile_m / BM) * 2 * (long)Cout);
+  }
 }
 
-template <int D, bool ACC>
+// part != nullptr (bf16 output, D == 1, no ACC): the STATS kernels, which also
+// fill part[ceil(M / 256)][2][Cout]
+template <int D, bool ACC, bool STATS = false>
 static void launch_conv(const void* X, const void* W9, const void* guard,
                         void* Y, int out_bf16, int N, int H, int W, int Cin,
                         int Cout, int OH, int OW, int S, int P, int taps,
-                        int fw, int pixst, int fd, hipStream_t s) {
+                        int fw, int pixst, int fd, hipStream_t s,
+                        float* part = nullptr) {
   const long M = (long)N * OH * OW;
   if (Cout >= 192) {
     int ntm = (int)((M + 255) / 256), ntn = (Cout + 255) / 256;
     dim3 grid(ntm * ntn);
     if (out_bf16)
-      hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 2, 4, 8, D, ACC>), grid,
+      hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 2, 4, 8, D, ACC, false, STATS>),
+                         grid,
                          dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
                          (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
                          OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
-                         fd);
+                         fd, part);
     else
       hipLaunchKernelGGL((conv3x3_kernel<float, 2, 4, 8, D, ACC>), grid,
                          dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
                          (const bf16_t*)guard, (float*)Y, N, H, W, Cin, Cout,
                          OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
-                         fd);
+                         fd, (float*)nullptr);
     return;
   }
   int ntm = (int)((M + 255) / 256), ntn = (Cout + 127) / 128;
   dim3 grid(ntm * ntn);
   if (out_bf16)
-    hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 4, 2, 4, D, ACC>), grid,
+    hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 4, 2, 4, D, ACC, false, STATS>),
+                       grid,
                        dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
                        (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
                        OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
-                         fd);
+                         fd, part);
   else
     hipLaunchKernelGGL((conv3x3_kernel<float, 4, 2, 4, D, ACC>), grid,
                        dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
                        (const bf16_t*)guard, (float*)Y, N, H, W, Cin, Cout,
                        OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
-                         fd);
+                         fd, (float*)nullptr);
 }
 
 extern "C" {
@@ -320,6 +343,17 @@ void tfosr_conv_mfma(const void* X, const void* W9, const void* guard, void* Y,
   }
 }
 
+// The plain forward (input dilation 1, bf16 output, no accumulation) of
+// tfosr_conv_mfma with the statistics epilogue: also fills
+// part[ceil(N*OH*OW / 256)][2][Cout] (both tile shapes have 256 rows).
+void tfosr_conv_mfma_stats(const void* X, const void* W9, const void* guard,
+                           void* Y, float* part, int N, int H, int W, int Cin,
+                           int Cout, int OH, int OW, int S, int P, int taps,
+                           int fw, int fd, hipStream_t s) {
+  launch_conv<1, false, true>(X, W9, guard, Y, /*out_bf16=*/1, N, H, W, Cin,
+                              Cout, OH, OW, S, P, taps, fw, Cin, fd, s, part);
+}
+
 // Parity-decomposed stride-2 backward-data / transposed-conv class launch:
 // computes the (oh0, ow0) output parity class over subsampled dims OHs x OWs
 // with ntaps class taps packed in tap_pack; writes strided pixels of the
@@ -337,13 +371,13 @@ void tfosr_conv_par(const void* X, const void* Wk, const void* guard, void* Y,
                          grid, dim3(512), 0, s, (const bf16_t*)X,
                          (const bf16_t*)Wk, (const bf16_t*)guard, (bf16_t*)Y,
                          N, H, W, Cin, Cout, OHs, OWs, 1, P, ntaps, 1, Cin,
-                         tap_pack, oh0, ow0, OWr, OHOWr, /*fd=*/1);
+                         tap_pack, oh0, ow0, OWr, OHOWr, /*fd=*/1, (float*)nullptr);
     else
       hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 2, 4, 8, 2, false, true>),
                          grid, dim3(512), 0, s, (const bf16_t*)X,
                          (const bf16_t*)Wk, (const bf16_t*)guard, (bf16_t*)Y,
                          N, H, W, Cin, Cout, OHs, OWs, 1, P, ntaps, 1, Cin,
-                         tap_pack, oh0, ow0, OWr, OHOWr, /*fd=*/1);
+                         tap_pack, oh0, ow0, OWr, OHOWr, /*fd=*/1, (float*)nullptr);
     return;
   }
   int ntm = (int)((M + 255) / 256), ntn = (Cout + 127) / 128;
@@ -353,13 +387,13 @@ void tfosr_conv_par(const void* X, const void* Wk, const void* guard, void* Y,
                        dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)Wk,
                        (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
                        OHs, OWs, 1, P, ntaps, 1, Cin, tap_pack, oh0, ow0,
-                       OWr, OHOWr, /*fd=*/1);
+                       OWr, OHOWr, /*fd=*/1, (float*)nullptr);
   else
     hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 4, 2, 4, 2, false, true>), grid,
                        dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)Wk,
                        (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
                        OHs, OWs, 1, P, ntaps, 1, Cin, tap_pack, oh0, ow0,
-                       OWr, OHOWr, /*fd=*/1);
+                       OWr, OHOWr, /*fd=*/1, (float*)nullptr);
 }
 
 // ResNet stem 7x7/s2 forward over a pre-padded NHWC4 image (x4 layout:

@@ -23,6 +23,7 @@
 // blockIdx -> tile mapping is XCD-aware (8 XCDs with private L2 on MI355X):
 // contiguous grid chunks land on one XCD so neighboring tiles share L2.
 #include "tfosr_common.h"
+#include "mfma_stats_epilogue.h"
 #include <type_traits>
 #include <cstdlib>
 #include <cstring>
@@ -41,10 +42,17 @@ __device__ __forceinline__ void stage16(const char* src,
       (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
 }
 
-template <typename OT, int WGM, int WGN, bool ACC = false>
+// STATS (bf16 output, non-accumulating only): after the tile stores, the block
+// also writes the tile's per-column BatchNorm partial (mean, M2) to row
+// tile_m / BM of part[ceil(M / BM)][2][N] — see mfma_stats_epilogue.h. The
+// stores themselves are the non-STATS kernel's. Needs K >= BK, so that the K
+// loop's closing barrier has retired every read of the staging ring.
+template <typename OT, int WGM, int WGN, bool ACC = false, bool STATS = false>
 __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
-    OT* __restrict__ C, int M, int N, int K) {
+    OT* __restrict__ C, int M, int N, int K, float* __restrict__ part) {
+  static_assert(!STATS || (!ACC && std::is_same<OT, bf16_t>::value),
+                "the statistics epilogue exists for plain bf16 stores only");
   constexpr int BM = WGM * 64;
   constexpr int BN = WGN * 64;
   constexpr int ABYTES = BM * BK * 2;  // 64 B per row
@@ -221,6 +229,12 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
       }
     }
   }
+  if constexpr (STATS) {
+    static_assert(TFOSR_TILE_STATS_LDS_FLOATS(WGM, BN) * 4 <= sizeof(lds), "");
+    mfma_tile_stats<4, WGM, BN>(acc, (float*)lds, wr, wc, lane, t, tile_m,
+                                tile_n, (long)M, N,
+                                part + (tile_m / BM) * 2 * (long)N);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -377,10 +391,49 @@ __global__ void mfma_probe_kernel(const short* __restrict__ a,
   for (int r = 0; r < 4; ++r) c[l * 4 + r] = acc[r];
 }
 
+// does the dispatch below send this shape to gemm_bt256_kernel?
+static bool gemm_route256(int M, int N, int K) {
+  static int use256 = -1;
+  if (use256 < 0) {
+    const char* e = getenv("TFOS_GEMM256");
+    use256 = (e == nullptr || strcmp(e, "off") != 0) ? 1 : 0;
+  }
+  return use256 && M >= 1024 && N >= 192 && K >= 1024;
+}
+
+static bool gemm_route_skinny(int N) {
+  return (N % 128 != 0) && (N % 64 == 0 || N <= 64);
+}
+
 extern "C" {
 
 void tfosr_gemm_bt_acc(const void*, const void*, void*, int, int, int, int,
                        int, hipStream_t);
+
+// Rows per tile of the statistics partials tfosr_gemm_bt_stats() writes for
+// this shape: part[ceil(M / rows)][2][N] floats. 0: the shape goes to
+// gemm_bt256_kernel, which has no statistics epilogue.
+int tfosr_gemm_bt_stats_rows(int M, int N, int K) {
+  if (gemm_route256(M, N, K)) return 0;
+  return gemm_route_skinny(N) ? 256 : 128;
+}
+
+// bf16 C = A @ B^T as tfosr_gemm_bt stores it, plus the per-tile BatchNorm
+// partials of C. Only for shapes with tfosr_gemm_bt_stats_rows() > 0.
+void tfosr_gemm_bt_stats(const void* A, const void* B, void* C, float* part,
+                         int M, int N, int K, hipStream_t s) {
+  if (gemm_route_skinny(N)) {
+    dim3 grid(((M + 255) / 256) * ((N + 63) / 64));
+    hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 4, 1, false, true>), grid,
+                       dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)B,
+                       (bf16_t*)C, M, N, K, part);
+    return;
+  }
+  dim3 grid(((M + 127) / 128) * ((N + 127) / 128));
+  hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 2, 2, false, true>), grid,
+                     dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)B,
+                     (bf16_t*)C, M, N, K, part);
+}
 
 void tfosr_gemm_bt(const void* A, const void* B, void* C, int out_bf16,
                    int M, int N, int K, hipStream_t s) {
@@ -394,12 +447,7 @@ void tfosr_gemm_bt_acc(const void* A, const void* B, void* C, int out_bf16,
   // 256^2 4-deep-pipelined kernel for large-K tiles (917 TF @4096^3 vs 644
   // for the 2-buffer kernel; the deep prologue loses on the skinny-K conv
   // shapes, which stay on the 128^2/256x64 kernels). Toggle: TFOS_GEMM256=off
-  static int use256 = -1;
-  if (use256 < 0) {
-    const char* e = getenv("TFOS_GEMM256");
-    use256 = (e == nullptr || strcmp(e, "off") != 0) ? 1 : 0;
-  }
-  if (use256 && M >= 1024 && N >= 192 && K >= 1024) {
+  if (gemm_route256(M, N, K)) {
     int ntm = (M + B2_BM - 1) / B2_BM, ntn = (N + B2_BN - 1) / B2_BN;
     dim3 grid(ntm * ntn);
     if (out_bf16) {
@@ -419,23 +467,22 @@ void tfosr_gemm_bt_acc(const void* A, const void* B, void* C, int out_bf16,
     return;
   }
   // skinny-N tile when it reduces waste (Cout=64 conv1x1 layers)
-  const bool skinny = (N % 128 != 0) && (N % 64 == 0 || N <= 64);
-  if (skinny) {
+  if (gemm_route_skinny(N)) {
     int ntm = (M + 255) / 256, ntn = (N + 63) / 64;
     dim3 grid(ntm * ntn);
     if (out_bf16) {
       if (accum)
         hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 4, 1, true>), grid,
                            dim3(256), 0, s, (const bf16_t*)A,
-                           (const bf16_t*)B, (bf16_t*)C, M, N, K);
+                           (const bf16_t*)B, (bf16_t*)C, M, N, K, nullptr);
       else
         hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 4, 1, false>), grid,
                            dim3(256), 0, s, (const bf16_t*)A,
-                           (const bf16_t*)B, (bf16_t*)C, M, N, K);
+                           (const bf16_t*)B, (bf16_t*)C, M, N, K, nullptr);
     } else {
       hipLaunchKernelGGL((gemm_bt_kernel<float, 4, 1>), grid, dim3(256), 0, s,
                          (const bf16_t*)A, (const bf16_t*)B, (float*)C, M, N,
-                         K);
+                         K, nullptr);
     }
     return;
   }
@@ -445,14 +492,14 @@ void tfosr_gemm_bt_acc(const void* A, const void* B, void* C, int out_bf16,
     if (accum)
       hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 2, 2, true>), grid, dim3(256),
                          0, s, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C,
-                         M, N, K);
+                         M, N, K, nullptr);
     else
       hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 2, 2, false>), grid,
                          dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)B,
-                         (bf16_t*)C, M, N, K);
+                         (bf16_t*)C, M, N, K, nullptr);
   } else {
     hipLaunchKernelGGL((gemm_bt_kernel<float, 2, 2>), grid, dim3(256), 0, s,
-                       (const bf16_t*)A, (const bf16_t*)B, (float*)C, M, N, K);
+                       (const bf16_t*)A, (const bf16_t*)B, (float*)C, M, N, K, nullptr);
   }
 }
 

@@ -1172,6 +1172,66 @@ class BucketAdam:
 # Fully-fused ResNet Bottleneck (manual backward, zero autograd glue)
 # ---------------------------------------------------------------------------
 
+def _bn_epi_mode():
+    """TFOS_BN_EPI: where the fused bottleneck's BatchNorms take their batch
+    statistics from. 'off': always the separate pass over the conv output
+    (stats_nhwc_fast); 'force': the conv kernel's statistics epilogue wherever
+    the dispatched kernel has one; 'auto' (default): per shape, _bn_epi_auto.
+    """
+    import os
+    mode = os.environ.get("TFOS_BN_EPI", "auto")
+    if mode not in ("auto", "off", "force"):
+        raise ValueError("TFOS_BN_EPI must be auto, off or force, got "
+                         + repr(mode))
+    return mode
+
+
+# smallest conv output, in bytes, that TFOS_BN_EPI=auto routes: the smallest
+# tensor of the measurement below (1024 x 512 x 7 x 7 bf16, 51 MB)
+_BN_EPI_MIN_BYTES = 1024 * 512 * 7 * 7 * 2
+
+
+def _bn_epi_auto(kind, M, K, cout):
+    """TFOS_BN_EPI=auto policy for one (conv, BN) pair: ``kind`` 'gemm' (a
+    1x1 stride-1 conv through gemm_bt) or 'conv' (conv_mfma), M output
+    pixels, K = taps * Cin, cout output channels.
+
+    Follows the per-pair measurement at the ResNet-50 batch-1024 shapes
+    (tools/bn_bench.py --epilogue; docs/performance.md "BN statistics from
+    the conv epilogues"): conv + statistics pass + merge against conv with
+    the epilogue + tile merge, medians of 9 alternating rounds, a pair being
+    ahead when it wins by more than either side's max - min over the rounds.
+
+      gemm_bt, 128^2 and 256x64 tiles (9 shapes)     10-28 % ahead  -> epilogue
+      conv_mfma, 256x256 tile (Cout >= 192)          4-13 % ahead   -> epilogue
+      conv_mfma, 256x128 tile (Cout < 192): 64->64 @56 loses 4.6 %, the two
+        128->128 shapes win by less than the spread                 -> pass
+
+    The 256x128 conv kernel has 4 waves stacked in M per column group and
+    spends in its epilogue what the pass over a 64- or 128-channel tensor
+    costs; it stays on the separate pass. Shapes that gemm_bt sends to its
+    256^2 kernel have no epilogue and come back without partials whatever
+    this says. Nothing smaller than the smallest tensor measured is routed:
+    at a few MB the pass runs from cache and launch count decides."""
+    if M * cout * 2 < _BN_EPI_MIN_BYTES:
+        return False
+    return kind == "gemm" or cout >= 192
+
+
+def _bn_epi_route(mode, kind, M, K, cout, ext=None):
+    """Does the (conv, BN) pair take the statistics-epilogue route? Under
+    'auto' and 'force' alike only where the BN that follows is on the NHWC
+    fast path (fewer than 2^31 elements, C % 8 == 0, C | 2048: what
+    ``ext.bn_fast_blocks`` answers): bn_fwd_train_pre takes nothing else, and
+    the generic kernels behind bn_fwd_train keep every other width working.
+    Without ``ext`` only the mode and the shape policy are consulted."""
+    if mode == "off":
+        return False
+    if ext is not None and ext.bn_fast_blocks(M * cout, cout, True, True) <= 0:
+        return False
+    return mode == "force" or _bn_epi_auto(kind, M, K, cout)
+
+
 class _BottleneckFn(torch.autograd.Function):
     """One autograd node for the whole bottleneck block.
 
@@ -1221,42 +1281,74 @@ class _BottleneckFn(torch.autograd.Function):
             w9 = w2.permute(0, 2, 3, 1).reshape(C2, 9 * C1) \
                 .to(torch.bfloat16).contiguous()
             w3b = w3.view(C3, C2).to(torch.bfloat16).contiguous()
-        t1 = as4d(ext.gemm_bt(as2d(x), w1b, True), H, W)
-        a1, m1, r1, k1 = ext.bn_fwd_train(t1, None, g1, b1, rm1, rv1,
-                                          momentum, eps, True)
-        t2 = ext.conv_mfma(a1, w9, C2, 3, 3, stride, 1, 1, -1, -1)
-        a2, m2, r2, k2 = ext.bn_fwd_train(t2, None, g2, b2, rm2, rv2,
-                                          momentum, eps, True)
-        OH, OW = t2.shape[2], t2.shape[3]
-        t3 = as4d(ext.gemm_bt(as2d(a2), w3b, True), OH, OW)
+        # TFOS_BN_EPI: a conv routed to its statistics-epilogue variant hands
+        # the BN that follows the tile partials of its output (part, rows), and
+        # that BN merges them instead of reading the tensor back; part is None
+        # for a conv left on the plain kernel or dispatched to a kernel
+        # without the epilogue, and its BN then runs the separate pass.
+        epi = _bn_epi_mode()
+
+        def gemm(a2d, wb):
+            if _bn_epi_route(epi, "gemm", a2d.shape[0], wb.shape[1],
+                             wb.shape[0], ext):
+                return ext.gemm_bt_stats(a2d, wb)
+            return ext.gemm_bt(a2d, wb, True), None, 0
+
+        def conv(a, wk, cout, k, s, p, m_out):
+            if _bn_epi_route(epi, "conv", m_out, k * k * a.shape[1], cout,
+                             ext):
+                return ext.conv_mfma_stats(a, wk, cout, k, k, s, p, 1, -1, -1)
+            return ext.conv_mfma(a, wk, cout, k, k, s, p, 1, -1, -1), None, 0
+
+        def bn(t, res, part, rows, g, b, rm, rv, relu):
+            if part is not None:
+                return ext.bn_fwd_train_pre(t, res, part, rows, g, b, rm, rv,
+                                            momentum, eps, relu)
+            return ext.bn_fwd_train(t, res, g, b, rm, rv, momentum, eps, relu)
+
+        OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+        t1, p1, n1 = gemm(as2d(x), w1b)
+        t1 = as4d(t1, H, W)
+        a1, m1, r1, k1 = bn(t1, None, p1, n1, g1, b1, rm1, rv1, True)
+        t2, p2, n2 = conv(a1, w9, C2, 3, stride, 1, N * OH * OW)
+        a2, m2, r2, k2 = bn(t2, None, p2, n2, g2, b2, rm2, rv2, True)
+        assert (OH, OW) == (t2.shape[2], t2.shape[3])
+        t3, p3, n3 = gemm(as2d(a2), w3b)
+        t3 = as4d(t3, OH, OW)
 
         if wd is not None:
             wdb = packs["wdb"].reshape(C3, Cin) if packs is not None \
                 else wd.view(C3, Cin).to(torch.bfloat16).contiguous()
             if stride == 1:
-                td = as4d(ext.gemm_bt(as2d(x), wdb, True), H, W)
+                td, pd, nd = gemm(as2d(x), wdb)
+                td = as4d(td, H, W)
             else:
-                td = ext.conv_mfma(x, wdb, C3, 1, 1, stride, 0, 1, -1, -1)
+                td, pd, nd = conv(x, wdb, C3, 1, stride, 0, N * OH * OW)
             import os
             dual = os.environ.get("TFOS_BN_DUAL", "on") != "off" \
                 and ext.bn_dual_eligible(t3, td)
             if dual:
                 # y = relu(bn3(t3) + bnd(td)) in one pass: the normalized
                 # shortcut is neither written nor saved
-                y, m3, r3, md, rd, k3 = ext.bn_dual_fwd_train(
-                    t3, td, g3, b3, rm3, rv3, gd, bd, rmd, rvd, momentum, eps)
+                if p3 is not None or pd is not None:
+                    y, m3, r3, md, rd, k3 = ext.bn_dual_fwd_train_pre(
+                        t3, td, p3, n3, pd, nd, g3, b3, rm3, rv3, gd, bd,
+                        rmd, rvd, momentum, eps)
+                else:
+                    y, m3, r3, md, rd, k3 = ext.bn_dual_fwd_train(
+                        t3, td, g3, b3, rm3, rv3, gd, bd, rmd, rvd, momentum,
+                        eps)
                 opt = [td, md, rd]
             else:
-                idn, md, rd, _kd = ext.bn_fwd_train(td, None, gd, bd, rmd,
-                                                    rvd, momentum, eps, False)
+                idn, md, rd, _kd = bn(td, None, pd, nd, gd, bd, rmd, rvd,
+                                      False)
                 opt = [td, idn, md, rd]
         else:
             dual = False
             idn = x
             opt = []
         if not dual:
-            y, m3, r3, k3 = ext.bn_fwd_train(t3, idn, g3, b3, rm3, rv3,
-                                             momentum, eps, True)
+            y, m3, r3, k3 = bn(t3, idn, p3, n3, g3, b3, rm3, rv3, True)
 
         ctx.save_for_backward(x, w1, g1, t1, a1, m1, r1, k1,
                               w2, g2, t2, a2, m2, r2, k2,

@@ -22,6 +22,11 @@ own, equal to its file name (compile bindings.cpp with
 ``bn_stage``: for an older commit, compile its csrc/bn_relu.hip with this
 commit's csrc/bindings.cpp.
 
+``--epilogue`` is a different table: per forward (conv, BN) pair of ResNet-50,
+the conv kernel followed by the statistics pass against the conv kernel with
+the statistics epilogue followed by the tile merge (see ``epilogue_main``); it
+is what the ``TFOS_BN_EPI=auto`` rule in ops/modules.py was read off.
+
 The variants timed are the ones the ResNet-50 step runs most: stats; apply
 with ReLU (and with ReLU + residual, ``apply+res``); bwd stats with the mask
 (and writing the gated gradient, ``bwd stats+g``); bwd dx with the mask.
@@ -108,6 +113,111 @@ def time_round(fn, iters):
     return a.elapsed_time(b) / iters   # ms
 
 
+# Forward (conv, BN) pairs of the ResNet-50 bottlenecks (the stem is a module
+# of its own): (kind, Cin, Cout, input H=W, kernel, stride, pairs per step).
+# 'gemm' is a 1x1 stride-1 conv through gemm_bt, 'conv' goes through conv_mfma.
+RESNET50_CONV_BN = [
+    ("gemm", 64, 64, 56, 1, 1, 1), ("gemm", 256, 64, 56, 1, 1, 2),
+    ("conv", 64, 64, 56, 3, 1, 3), ("gemm", 64, 256, 56, 1, 1, 4),
+    ("gemm", 256, 128, 56, 1, 1, 1), ("conv", 128, 128, 56, 3, 2, 1),
+    ("gemm", 128, 512, 28, 1, 1, 4), ("conv", 256, 512, 56, 1, 2, 1),
+    ("gemm", 512, 128, 28, 1, 1, 3), ("conv", 128, 128, 28, 3, 1, 3),
+    ("gemm", 512, 256, 28, 1, 1, 1), ("conv", 256, 256, 28, 3, 2, 1),
+    ("gemm", 256, 1024, 14, 1, 1, 6), ("conv", 512, 1024, 28, 1, 2, 1),
+    ("gemm", 1024, 256, 14, 1, 1, 5), ("conv", 256, 256, 14, 3, 1, 5),
+    ("gemm", 1024, 512, 14, 1, 1, 1), ("conv", 512, 512, 14, 3, 2, 1),
+    ("gemm", 512, 2048, 7, 1, 1, 3), ("conv", 1024, 2048, 14, 1, 2, 1),
+    ("gemm", 2048, 512, 7, 1, 1, 2), ("conv", 512, 512, 7, 3, 1, 2),
+]
+
+
+def epilogue_main(args):
+    """--epilogue: per (conv, BN) pair, the plain conv kernel followed by the
+    statistics pass over its output and that pass's merge (``old``) against
+    the conv kernel with the statistics epilogue followed by the tile merge
+    (``new``); neither side runs the BN apply. Both alternate inside every
+    round; the columns are the medians over the rounds, each side's spread
+    (max - min over the rounds) and the conv kernels alone, which shows what
+    the epilogue itself costs. A pair counts as ahead when old - new exceeds
+    the larger of the two spreads."""
+    from tensorflowonspark_amd.ops import get_ext
+    ext = get_ext(required=True)
+    N, dev = args.batch, "cuda"
+    print("batch {}: ms per (conv + statistics), median of {} rounds x {} "
+          "launches".format(N, args.rounds, args.iters))
+    print("{:<5s}{:>5s}{:>5s}{:>4s} k s  n {:>7s} | {:>8s} {:>8s} {:>7s} "
+          "{:>7s} | {:>8s} {:>8s} | {:>8s} {}".format(
+              "kind", "Cin", "Cout", "H", "MB", "old", "new", "sprd o",
+              "sprd n", "conv", "conv+epi", "old-new", "verdict"))
+    step_old = step_new = step_auto = 0.0
+    for kind, cin, cout, H, k, stride, count in RESNET50_CONV_BN:
+        OH = (H - 1) // stride + 1
+        x = torch.randn(N, cin, H, H, device=dev).to(torch.bfloat16) \
+            .contiguous(memory_format=torch.channels_last)
+        w = (torch.randn(cout, k * k * cin, device=dev)
+             / (k * k * cin) ** 0.5).to(torch.bfloat16)
+        rm, rv = torch.zeros(cout, device=dev), torch.ones(cout, device=dev)
+        x2d = x.permute(0, 2, 3, 1).reshape(-1, cin)
+
+        def as4d(t):
+            return t.view(N, OH, OH, cout).permute(0, 3, 1, 2)
+
+        if kind == "gemm":
+            def plain():
+                return as4d(ext.gemm_bt(x2d, w, True))
+
+            def fused():
+                t, part, rows = ext.gemm_bt_stats(x2d, w)
+                return as4d(t), part, rows
+        else:
+            def plain():
+                return ext.conv_mfma(x, w, cout, k, k, stride, k // 2, 1, -1,
+                                     -1)
+
+            def fused():
+                return ext.conv_mfma_stats(x, w, cout, k, k, stride, k // 2,
+                                           1, -1, -1)
+
+        def old():
+            ext.bn_batch_stats(plain(), None, 0, rm, rv, 0.1, 1e-5)
+
+        def new():
+            t, part, rows = fused()
+            ext.bn_batch_stats(t, part, rows, rm, rv, 0.1, 1e-5)
+
+        has_epi = fused()[1] is not None
+        calls = [("old", old), ("new", new), ("conv", plain),
+                 ("conv+epi", fused)]
+        for _, fn in calls:
+            fn()
+        torch.cuda.synchronize()
+        ms = {n: [] for n, _ in calls}
+        for _ in range(args.rounds):
+            for n, fn in calls:
+                ms[n].append(time_round(fn, args.iters))
+        med = {n: statistics.median(v) for n, v in ms.items()}
+        spread = {n: max(v) - min(v) for n, v in ms.items()}
+        gain = med["old"] - med["new"]
+        if not has_epi:
+            verdict = "no epilogue (256^2 GEMM route)"
+        elif gain > max(spread["old"], spread["new"]):
+            verdict = "ahead"
+        else:
+            verdict = "not ahead"
+        step_old += count * med["old"]
+        step_new += count * med["new"]
+        step_auto += count * (med["new"] if verdict == "ahead" else med["old"])
+        print("{:<5s}{:5d}{:5d}{:4d} {} {} {:2d} {:7.0f} | {:8.4f} {:8.4f} "
+              "{:7.4f} {:7.4f} | {:8.4f} {:8.4f} | {:8.4f} {}".format(
+                  kind, cin, cout, H, k, stride, count,
+                  N * OH * OH * cout * 2 / 1e6, med["old"], med["new"],
+                  spread["old"], spread["new"], med["conv"], med["conv+epi"],
+                  gain, verdict), flush=True)
+        del x, w, x2d
+    print("per step (pairs x medians), ms: old {:.3f}  new everywhere {:.3f}  "
+          "new where ahead {:.3f}".format(step_old, step_new, step_auto))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -116,9 +226,14 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--ext", action="append", default=[], metavar="NAME=PATH",
                     help="another build of the extension to alternate with")
+    ap.add_argument("--epilogue", action="store_true",
+                    help="per ResNet-50 (conv, BN) pair: statistics from the "
+                         "conv epilogue vs the separate pass")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bn_bench needs a GPU")
+    if args.epilogue:
+        return epilogue_main(args)
     from tensorflowonspark_amd.ops import get_ext
     exts = [("tree", get_ext(required=True))]
     for spec in args.ext:

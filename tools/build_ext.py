@@ -52,7 +52,8 @@ def build(verbose=True):
         path = os.path.join(CSRC, src)
         obj = os.path.join(BUILD, os.path.splitext(src)[0] + ".o")
         objs.append(obj)
-        deps = [path, os.path.join(CSRC, "tfosr_common.h")]
+        deps = [path, os.path.join(CSRC, "tfosr_common.h"),
+                os.path.join(CSRC, "mfma_stats_epilogue.h")]
         if (os.path.exists(obj)
                 and all(os.path.getmtime(obj) > os.path.getmtime(d) for d in deps)):
             continue
