@@ -6,28 +6,103 @@ hand-written gfx950 kernel from ``csrc/`` and whose CPU path is the fp32
 reference implementation the numerics tests compare against.
 """
 
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import get_ext
+from .packplan import (EagerPacks, _class_taps, flipped, im2col,
+                       parity_class, rows, rows_t, stem_w224)
 
 
+def _cl_bf16(t):
+    """An upstream gradient as the kernels take it: channels_last bf16."""
+    return t.contiguous(memory_format=torch.channels_last).to(torch.bfloat16)
 
 
-def _use_wrw2(k, cin, cout):
-    """Weight-gradient backend routing. TFOS_WRW: auto (default) routes each
-    shape to the measured-faster implementation (MI355X b1024, see
-    profiles/README.md — the in-tree transpose-read wrw kernel wins on
-    small-channel 3x3 and is within 0.75-1.2x of the library igemm
-    elsewhere); mfma2 forces the in-tree kernel, miopen the library."""
-    import os
-    mode = os.environ.get("TFOS_WRW", "auto")
+def as2d(t):
+    """channels_last [N, C, H, W] viewed as the [N*H*W, C] GEMM operand."""
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+
+
+def as4d(t2d, n, h, w):
+    return t2d.view(n, h, w, -1).permute(0, 3, 1, 2)
+
+
+def _use_wrw2(k, cin, cout, mode=None):
+    """Does TFOS_WRW (``mode``; None reads the environment) send this shape
+    to the transpose-read kernel conv_wrw2? auto (default, and any unknown
+    string) routes each shape to the measured-faster implementation (MI355X
+    b1024, see profiles/README.md — the in-tree kernel wins on small-channel
+    3x3 and is within 0.75-1.2x of the library igemm elsewhere); mfma2
+    forces the in-tree kernel, miopen and mfma do not use it."""
+    if mode is None:
+        mode = os.environ.get("TFOS_WRW", "auto")
     if mode == "mfma2":
         return True
     if mode in ("miopen", "mfma"):
         return False
     return k == 3 and cin <= 64 and cout <= 64
+
+
+def _wrw_backend(mode, k, cin, cout, stride, fd=1, transposed=False,
+                 round1=True):
+    """Which implementation computes a conv's weight gradient under
+    TFOS_WRW=mode: 'wrw2', 'wrw' or 'lib'. See _weight_grad."""
+    ch8 = cin % 8 == 0 and cout % 8 == 0
+    if transposed:
+        return "lib"
+    if ch8 and _use_wrw2(k, cin, cout, mode):
+        return "wrw2"
+    if round1 and mode == "mfma" and stride == 1 and fd == 1 and ch8:
+        return "wrw"
+    return "lib"
+
+
+def _lib_conv_backward(dy, x, weight, stride, pad, fd, transposed, mask):
+    """(dx, dw) of a conv from the library, each where mask says so."""
+    w4 = weight.to(torch.bfloat16).contiguous(
+        memory_format=torch.channels_last)
+    gx, gw, _ = torch.ops.aten.convolution_backward(
+        dy, x, w4, None, [stride, stride], [pad, pad], [fd, fd], transposed,
+        [0, 0], 1, [mask[0], mask[1], False])
+    return gx, gw
+
+
+def _weight_grad(dy, x, weight, k, stride, pad, fd=1, transposed=False,
+                 round1=True):
+    """dW of a k x k conv (filter dilation fd; ``transposed``: of a
+    ConvTranspose2d) from channels_last bf16 dy and the saved input x, in
+    the weight's own shape and dtype. The one place TFOS_WRW is acted on:
+
+      conv_wrw2  the transpose-read MFMA kernel (any stride and dilation),
+                 where _use_wrw2 says so: under mfma2 always, under auto for
+                 3x3 with both channel counts <= 64; channels % 8 == 0
+      conv_wrw   the round-1 TN kernel, kept for comparison: only under
+                 mfma, stride 1, undilated, channels % 8 == 0, and not
+                 where the caller passes round1=False
+      library    _lib_conv_backward (aten, on a channels_last bf16 weight):
+                 everything else (miopen, most of auto), every transposed conv
+    """
+    cout, cin = weight.shape[0], weight.shape[1]
+    backend = _wrw_backend(os.environ.get("TFOS_WRW", "auto"), k, cin, cout,
+                           stride, fd, transposed, round1)
+    if backend == "lib":
+        dw = _lib_conv_backward(dy, x, weight, stride, pad, fd, transposed,
+                                (False, True))[1]
+        return dw.to(weight.dtype)
+    ext = get_ext(required=True)
+    if backend == "wrw2":
+        dw = ext.conv_wrw2(dy, x, k, k, stride, pad,
+                           **({"fd": fd} if fd != 1 else {}))
+    else:
+        dw = ext.conv_wrw(dy, x, k, k, pad)
+    # [Cout, taps*Cin], tap-major, back to [Cout, Cin, k, k]
+    dw = dw.view(cout, cin, 1, 1) if k == 1 else \
+        dw.view(cout, k, k, cin).permute(0, 3, 1, 2).contiguous()
+    return dw.to(weight.dtype)
 
 
 # ---------------------------------------------------------------------------
@@ -425,44 +500,29 @@ class _Conv1x1S2Fn(torch.autograd.Function):
     """Stride-2 1x1 conv (ResNet downsample path) on the implicit-GEMM MFMA
     kernel: forward is taps=1/S=2; backward-data is the input-dilated (D=2)
     variant of the same kernel (dx = scatter of dy @ W, computed gather-side);
-    weight-grad reduces over the subsampled pixels via the library igemm until
-    conv_wrw covers stride 2."""
+    weight-grad: _weight_grad."""
 
     @staticmethod
     def forward(ctx, x, weight):
         ext = get_ext(required=True)
-        Cout, Cin = weight.shape[0], weight.shape[1]
         if x.dtype != torch.bfloat16:
             x = x.to(torch.bfloat16)
-        w2d = weight.view(Cout, Cin).to(torch.bfloat16).contiguous()
-        y = ext.conv_mfma(x, w2d, Cout, 1, 1, 2, 0, 1, -1, -1)
+        y = ext.conv_mfma(x, rows(weight), weight.shape[0], 1, 1, 2, 0, 1,
+                          -1, -1)
         ctx.save_for_backward(x, weight)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        ext = get_ext(required=True)
         x, weight = ctx.saved_tensors
         Cout, Cin = weight.shape[0], weight.shape[1]
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        wT = weight.view(Cout, Cin).t().to(torch.bfloat16).contiguous()
+        dy = _cl_bf16(dy)
         # dx[h,w] = (h,w even) ? dy[h/2,w/2] @ W : 0 — only the even-even
         # parity class has a tap; zero-fill and launch just that class
         dx = torch.zeros(x.shape, device=x.device, dtype=torch.bfloat16) \
             .contiguous(memory_format=torch.channels_last)
-        _conv_parity(dy, wT.view(Cin, 1, 1, Cout), dx, 1, 0)
-        import os
-        if Cin % 8 == 0 and Cout % 8 == 0 and _use_wrw2(1, Cin, Cout):
-            dw = ext.conv_wrw2(dy, x, 1, 1, 2, 0).view(Cout, Cin, 1, 1)
-        else:
-            w4 = weight.to(torch.bfloat16).contiguous(
-                memory_format=torch.channels_last)
-            _, dw, _ = torch.ops.aten.convolution_backward(
-                dy, x, w4, None, [2, 2], [0, 0], [1, 1], False, [0, 0], 1,
-                [False, True, False])
-        return dx, dw.to(weight.dtype)
+        _conv_parity(dy, rows_t(weight).view(Cin, 1, 1, Cout), dx, 1, 0)
+        return dx, _weight_grad(dy, x, weight, 1, 2, 0)
 
 
 class _Conv1x1Fn(torch.autograd.Function):
@@ -470,54 +530,30 @@ class _Conv1x1Fn(torch.autograd.Function):
 
     forward / input-grad run on the hand-written gfx950 MFMA kernel
     (C = A @ B^T, K-contiguous operands); the weight-grad contraction
-    (reduction over the huge M dim) goes through rocBLAS/hipBLASLt — a plain
-    library GEMM, per the kernel-usage policy."""
+    (dW = dy^T @ x, a reduction over the huge M dim): _weight_grad."""
 
     @staticmethod
     def forward(ctx, x, weight):
         ext = get_ext(required=True)
-        N, Cin, H, W = x.shape
-        Cout = weight.shape[0]
+        N, _, H, W = x.shape
         # channels_last storage viewed as the [M, Cin] activation matrix
-        x2d = x.permute(0, 2, 3, 1).reshape(N * H * W, Cin)
+        x2d = as2d(x)
         if x2d.dtype != torch.bfloat16:
             x2d = x2d.to(torch.bfloat16)
-        w2d = weight.view(Cout, Cin).to(torch.bfloat16)
+        w2d = rows(weight)
         y2d = ext.gemm_bt(x2d, w2d, True)
-        ctx.save_for_backward(x2d, w2d)
-        ctx.dims = (N, H, W, Cin, Cout, weight.dtype)
-        return y2d.view(N, H, W, Cout).permute(0, 3, 1, 2)
+        ctx.save_for_backward(x2d, w2d, weight)
+        return as4d(y2d, N, H, W)
 
     @staticmethod
     def backward(ctx, dy):
         ext = get_ext(required=True)
-        x2d, w2d = ctx.saved_tensors
-        N, H, W, Cin, Cout, wdtype = ctx.dims
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        dy2d = dy.permute(0, 2, 3, 1).reshape(N * H * W, Cout)
+        x2d, w2d, weight = ctx.saved_tensors
+        N, _, H, W = dy.shape
+        dy = _cl_bf16(dy)
         # dx[M,Cin] = dy[M,Cout] @ W[Cout,Cin]  ->  gemm_bt(dy, W^T)
-        dx2d = ext.gemm_bt(dy2d, w2d.t().contiguous(), True)
-        dx = dx2d.view(N, H, W, Cin).permute(0, 3, 1, 2)
-        # dW[Cout,Cin] = dy^T @ x: a reduction over the huge M dim.
-        # TFOS_WRW: mfma2 (default, transpose-read MFMA kernel), mfma
-        # (round-1 TN kernel), miopen (library igemm; hipBLASLt's split-K
-        # pick was ~7x slower than either).
-        import os
-        wrw = os.environ.get("TFOS_WRW", "auto")
-        x4d = x2d.view(N, H, W, Cin).permute(0, 3, 1, 2)
-        if Cin % 8 == 0 and Cout % 8 == 0 and _use_wrw2(1, Cin, Cout):
-            dw = ext.conv_wrw2(dy, x4d, 1, 1, 1, 0).view(Cout, Cin, 1, 1)
-        elif wrw == "mfma" and Cin % 8 == 0 and Cout % 8 == 0:
-            ext2 = get_ext(required=True)
-            dw = ext2.conv_wrw(dy, x4d, 1, 1, 0).view(Cout, Cin, 1, 1)
-        else:
-            w4d = w2d.view(Cout, Cin, 1, 1)
-            _, dw, _ = torch.ops.aten.convolution_backward(
-                dy, x4d, w4d, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-                [False, True, False])
-        return dx, dw.to(wdtype)
+        dx = as4d(ext.gemm_bt(as2d(dy), rows_t(w2d), True), N, H, W)
+        return dx, _weight_grad(dy, as4d(x2d, N, H, W), weight, 1, 1, 0)
 
 
 class Conv1x1(nn.Module):
@@ -538,7 +574,6 @@ class Conv1x1(nn.Module):
         self._s2_ok = stride == 2 and cin % 32 == 0 and cout % 32 == 0
 
     def forward(self, x):
-        import os
         backend = os.environ.get("TFOS_CONV1X1", "mfma")
         # the MFMA kernel is bf16-only: a silent downcast would corrupt a
         # claimed-fp32 run, so other dtypes use the library conv
@@ -572,57 +607,36 @@ class Conv1x1(nn.Module):
 class _Conv3x3Fn(torch.autograd.Function):
     """3x3/pad-1 conv (stride 1 or 2) on channels_last bf16 via the
     4-deep-pipelined implicit-GEMM kernel. dgrad = dilated-input conv of dy
-    with the flipped/transposed weight (same kernel, D=S); wrw goes through
-    MIOpen's tuned igemm by default (TFOS_WRW=mfma for the in-tree kernel)."""
+    with the flipped/transposed weight (same kernel, D=S; parity-decomposed
+    for stride 2); wrw: _weight_grad."""
 
     @staticmethod
     def forward(ctx, x, weight, stride):
         ext = get_ext(required=True)
-        Cout, Cin = weight.shape[0], weight.shape[1]
         if x.dtype != torch.bfloat16:
             x = x.to(torch.bfloat16)
-        w9 = weight.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin)             .to(torch.bfloat16).contiguous()
-        y = ext.conv_mfma(x, w9, Cout, 3, 3, stride, 1, 1, -1, -1)
+        y = ext.conv_mfma(x, im2col(weight), weight.shape[0], 3, 3, stride,
+                          1, 1, -1, -1)
         ctx.save_for_backward(x, weight)
         ctx.stride = stride
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        ext = get_ext(required=True)
         x, weight = ctx.saved_tensors
         S = ctx.stride
         Cout, Cin = weight.shape[0], weight.shape[1]
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        # W'[cin][r][s][cout] = W[cout][2-r][2-s][cin]
-        wperm = weight.flip(2, 3).permute(1, 2, 3, 0) \
-            .to(torch.bfloat16).contiguous()
+        dy = _cl_bf16(dy)
+        wperm = flipped(weight)
         if S == 2:
             dx = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16) \
                 .contiguous(memory_format=torch.channels_last)
             _conv_parity(dy, wperm, dx, 3, 1)
         else:
-            dx = ext.conv_mfma(dy, wperm.reshape(Cin, 9 * Cout), Cin,
-                               3, 3, 1, 1, 1, x.shape[2], x.shape[3])
-        import os
-        wrw = os.environ.get("TFOS_WRW", "auto")
-        if Cin % 8 == 0 and Cout % 8 == 0 and _use_wrw2(3, Cin, Cout):
-            # transpose-read MFMA wrw kernel (stride 1 and 2)
-            dw9 = ext.conv_wrw2(dy, x, 3, 3, S, 1)
-            dw = dw9.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
-        elif wrw == "mfma" and S == 1:
-            # round-1 TN kernel (kept for comparison)
-            dw9 = ext.conv_wrw(dy, x, 3, 3, 1)
-            dw = dw9.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
-        else:
-            w4 = weight.to(torch.bfloat16).contiguous(
-                memory_format=torch.channels_last)
-            _, dw, _ = torch.ops.aten.convolution_backward(
-                dy, x, w4, None, [S, S], [1, 1], [1, 1], False, [0, 0], 1,
-                [False, True, False])
-        return dx, dw.to(weight.dtype), None
+            dx = get_ext(required=True).conv_mfma(
+                dy, wperm.reshape(Cin, 9 * Cout), Cin, 3, 3, 1, 1, 1,
+                x.shape[2], x.shape[3])
+        return dx, _weight_grad(dy, x, weight, 3, S, 1), None
 
 
 class Conv3x3(nn.Module):
@@ -641,9 +655,10 @@ class Conv3x3(nn.Module):
             and stride in (1, 2)
 
     def forward(self, x):
-        import os
         backend = os.environ.get("TFOS_CONV3X3", "mfma")
-        if x.is_cuda and self._eligible and backend == "mfma"                 and x.dtype == torch.bfloat16                 and get_ext(required=True) is not None:
+        if x.is_cuda and self._eligible and backend == "mfma" \
+                and x.dtype == torch.bfloat16 \
+                and get_ext(required=True) is not None:
             x = x.contiguous(memory_format=torch.channels_last)
             return _Conv3x3Fn.apply(x, self.weight, self.stride)
         return F.conv2d(x, self.weight.to(x.dtype), padding=1,
@@ -708,7 +723,6 @@ def _atrous_auto(path, M, cin, cout):
 def _atrous_route(N, H, W, cin, cout, fd):
     """(collapse, fwd_in_tree, dgrad_in_tree) for TFOS_ATROUS, or None for
     the plain library conv."""
-    import os
     mode = os.environ.get("TFOS_ATROUS", "auto")
     if mode == "miopen":
         return None
@@ -732,18 +746,16 @@ class _AtrousConv3x3Fn(torch.autograd.Function):
     """3x3 conv with filter dilation fd, stride 1, padding fd, on
     channels_last bf16. Forward is the implicit-GEMM kernel with tap offsets
     (r*fd, s*fd); dgrad is the SAME kernel run on dy with the flipped and
-    transposed weight, dilation fd and pad 2*fd - fd = fd; wrw is the
-    transpose-read kernel with the same tap offsets when _use_wrw2 routes it
-    in-tree. A direction routed to the library goes through aten."""
+    transposed weight, dilation fd and pad 2*fd - fd = fd; wrw: _weight_grad
+    with the same tap offsets. A forward or dgrad routed to the library goes
+    through aten."""
 
     @staticmethod
     def forward(ctx, x, weight, fd, fwd_in_tree, dgrad_in_tree):
-        ext = get_ext(required=True)
-        Cout, Cin = weight.shape[0], weight.shape[1]
         if fwd_in_tree:
-            w9 = weight.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin) \
-                .to(torch.bfloat16).contiguous()
-            y = ext.conv_mfma(x, w9, Cout, 3, 3, 1, fd, 1, -1, -1, fd=fd)
+            y = get_ext(required=True).conv_mfma(
+                x, im2col(weight), weight.shape[0], 3, 3, 1, fd, 1, -1, -1,
+                fd=fd)
         else:
             y = F.conv2d(x, weight.to(torch.bfloat16), None, 1, fd, fd)
         ctx.save_for_backward(x, weight)
@@ -753,41 +765,20 @@ class _AtrousConv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        ext = get_ext(required=True)
         x, weight = ctx.saved_tensors
         fd = ctx.fd
         Cout, Cin = weight.shape[0], weight.shape[1]
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        wrw_in_tree = Cin % 8 == 0 and Cout % 8 == 0 \
-            and _use_wrw2(3, Cin, Cout)
+        dy = _cl_bf16(dy)
         dx = dw = None
-        if need_dx and ctx.dgrad_in_tree:
-            # W'[cin][r][s][cout] = W[cout][2-r][2-s][cin]
-            wperm = weight.flip(2, 3).permute(1, 2, 3, 0) \
-                .to(torch.bfloat16).contiguous()
-            dx = ext.conv_mfma(dy, wperm.reshape(Cin, 9 * Cout), Cin, 3, 3,
-                               1, 2 * fd - fd, 1, x.shape[2], x.shape[3],
-                               fd=fd)
-        if need_dw and wrw_in_tree:
-            dw9 = ext.conv_wrw2(dy, x, 3, 3, 1, fd, fd=fd)
-            dw = dw9.view(Cout, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
-        lib_dx = need_dx and dx is None
-        lib_dw = need_dw and dw is None
-        if lib_dx or lib_dw:
-            w4 = weight.to(torch.bfloat16).contiguous(
-                memory_format=torch.channels_last)
-            gx, gw, _ = torch.ops.aten.convolution_backward(
-                dy, x, w4, None, [1, 1], [fd, fd], [fd, fd], False, [0, 0],
-                1, [lib_dx, lib_dw, False])
-            if lib_dx:
-                dx = gx
-            if lib_dw:
-                dw = gw
-        if dw is not None:
-            dw = dw.to(weight.dtype)
+        if ctx.needs_input_grad[0] and ctx.dgrad_in_tree:
+            dx = get_ext(required=True).conv_mfma(
+                dy, flipped(weight).reshape(Cin, 9 * Cout), Cin, 3, 3,
+                1, 2 * fd - fd, 1, x.shape[2], x.shape[3], fd=fd)
+        elif ctx.needs_input_grad[0]:
+            dx = _lib_conv_backward(dy, x, weight, 1, fd, fd, False,
+                                    (True, False))[0]
+        if ctx.needs_input_grad[1]:
+            dw = _weight_grad(dy, x, weight, 3, 1, fd, fd)
         return dx, dw, None, None, None
 
 
@@ -864,23 +855,27 @@ class DilatedConv3x3(nn.Conv2d):
         return new
 
 
-
-
-def _conv_parity_packed(x, packs, prefix, out, k, pp, accum=False):
-    """Parity classes with pre-packed per-class weights (PackPlan views
-    named '<prefix>_<ph><pw>' shaped [OC, nr, ns, KC])."""
+def _parity_launch(x, class_weight, out, k, pp, accum):
+    """One conv_par launch per non-empty output parity class, each with only
+    its valid taps; class_weight(ph, pw, rl, sl) is [OC, nr, ns, KC]."""
     ext = get_ext(required=True)
-    from .packplan import _class_taps
     for (ph, pw), (rl, sl) in _class_taps(k, pp).items():
         if not rl or not sl or ph >= out.shape[2] or pw >= out.shape[3]:
             continue
-        wk = packs["{}_{}{}".format(prefix, ph, pw)]
-        oc = wk.shape[-4] if wk.dim() == 4 else wk.shape[0]
-        wk2 = wk.reshape(oc, -1)
-        taps_r = [r for r in rl for _ in sl]
-        taps_s = [s2 for _ in rl for s2 in sl]
-        ext.conv_par(x, wk2, out, taps_r, taps_s, pp, accum)
+        wk = class_weight(ph, pw, rl, sl)
+        ext.conv_par(x, wk.reshape(wk.shape[0], -1), out,
+                     [r for r in rl for _ in sl], [s for _ in rl for s in sl],
+                     pp, accum)
     return out
+
+
+def _conv_parity_packed(x, packs, prefix, out, k, pp, accum=False):
+    """_conv_parity with per-class weights already laid out: packs[
+    '<prefix>_<ph><pw>'] shaped [OC, nr, ns, KC] (PackPlan views or
+    EagerPacks)."""
+    return _parity_launch(
+        x, lambda ph, pw, rl, sl: packs["{}_{}{}".format(prefix, ph, pw)],
+        out, k, pp, accum)
 
 
 def _conv_parity(x, wperm, out, k, pp, accum=False):
@@ -893,21 +888,9 @@ def _conv_parity(x, wperm, out, k, pp, accum=False):
     transposed-conv use); out: [N, OC, OH, OW] cl bf16 (every pixel of every
     non-empty class gets written; for k==1 zero-fill `out` first —
     odd-parity classes have no taps)."""
-    ext = get_ext(required=True)
-    OC = wperm.shape[0]
-    KC = wperm.shape[3]
-    for ph in (0, 1):
-        for pw in (0, 1):
-            taps = [(r, s) for r in range(k) for s in range(k)
-                    if (ph - pp + r) % 2 == 0 and (pw - pp + s) % 2 == 0]
-            if not taps or ph >= out.shape[2] or pw >= out.shape[3]:
-                continue
-            wk = torch.stack([wperm[:, r, s, :] for r, s in taps], dim=1) \
-                .reshape(OC, len(taps) * KC).contiguous()
-            ext.conv_par(x, wk, out,
-                         [r for r, _ in taps], [s for _, s in taps],
-                         pp, accum)
-    return out
+    return _parity_launch(
+        x, lambda ph, pw, rl, sl: parity_class(wperm, rl, sl),
+        out, k, pp, accum)
 
 
 # ---------------------------------------------------------------------------
@@ -923,24 +906,20 @@ class _ConvT2dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, stride, padding, output_padding):
-        ext = get_ext(required=True)
-        Cin, Cout, KH, KW = weight.shape
+        _, Cout, KH, KW = weight.shape
         if x.dtype != torch.bfloat16:
             x = x.to(torch.bfloat16)
         # W'[cout][r][s][cin] = W[cin][cout][KH-1-r][KW-1-s]
-        wperm = weight.flip(2, 3).permute(1, 2, 3, 0) \
-            .to(torch.bfloat16).contiguous()
+        wperm = flipped(weight)
         H, W = x.shape[2], x.shape[3]
         OH = (H - 1) * stride - 2 * padding + KH + output_padding
         OW = (W - 1) * stride - 2 * padding + KW + output_padding
         y = torch.empty(x.shape[0], Cout, OH, OW, device=x.device,
                         dtype=torch.bfloat16) \
             .contiguous(memory_format=torch.channels_last)
-        if KH % 2 == 0 and output_padding == 0:
-            _conv_parity(x, wperm, y, KH, KH - 1 - padding)
-        else:  # odd kernels / output_padding: some classes empty -> zero base
+        if KH % 2 or output_padding:  # some classes empty -> zero base
             y.zero_()
-            _conv_parity(x, wperm, y, KH, KH - 1 - padding)
+        _conv_parity(x, wperm, y, KH, KH - 1 - padding)
         ctx.save_for_backward(x, weight)
         ctx.params = (stride, padding)
         return y
@@ -950,20 +929,13 @@ class _ConvT2dFn(torch.autograd.Function):
         ext = get_ext(required=True)
         x, weight = ctx.saved_tensors
         S, P = ctx.params
-        Cin, Cout, KH, KW = weight.shape
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
+        Cin, _, KH, KW = weight.shape
+        dy = _cl_bf16(dy)
         # dx = plain stride-S conv of dy with W (no flip/swap)
-        wd = weight.permute(0, 2, 3, 1).reshape(Cin, KH * KW * Cout)             .to(torch.bfloat16).contiguous()
-        dx = ext.conv_mfma(dy, wd, Cin, KH, KW, S, P, 1,
+        dx = ext.conv_mfma(dy, im2col(weight), Cin, KH, KW, S, P, 1,
                            x.shape[2], x.shape[3])
-        w4 = weight.to(torch.bfloat16).contiguous(
-            memory_format=torch.channels_last)
-        _, dw, _ = torch.ops.aten.convolution_backward(
-            dy, x, w4, None, [S, S], [P, P], [1, 1], True, [0, 0], 1,
-            [False, True, False])
-        return dx, dw.to(weight.dtype), None, None, None
+        dw = _weight_grad(dy, x, weight, KH, S, P, transposed=True)
+        return dx, dw, None, None, None
 
 
 class ConvTranspose2dMFMA(nn.Module):
@@ -985,7 +957,6 @@ class ConvTranspose2dMFMA(nn.Module):
         self._eligible = cin % 32 == 0 and cout % 32 == 0 and stride == 2
 
     def forward(self, x):
-        import os
         # tiny decoders (e.g. 4x4 spatial at the U-Net bottom) under-fill the
         # 256-row implicit-GEMM tiles; those stay on the library conv
         big = x.shape[0] * x.shape[2] * x.shape[3] * 4 >= 32768
@@ -1111,7 +1082,8 @@ class Conv2dIm2colMFMA(nn.Module):
             y2 = _GemmBTFn.apply(a, w2)                   # [N*L, Cout]
             if self.bias is not None:
                 y2 = y2 + self.bias.to(y2.dtype)
-            return y2.view(N, OH * OW, Cout).transpose(1, 2)                 .reshape(N, Cout, OH, OW)
+            return y2.view(N, OH * OW, Cout).transpose(1, 2) \
+                .reshape(N, Cout, OH, OW)
         b = None if self.bias is None else self.bias.to(x.dtype)
         return F.conv2d(x, self.weight.to(x.dtype), b)
 
@@ -1178,7 +1150,6 @@ def _bn_epi_mode():
     (stats_nhwc_fast); 'force': the conv kernel's statistics epilogue wherever
     the dispatched kernel has one; 'auto' (default): per shape, _bn_epi_auto.
     """
-    import os
     mode = os.environ.get("TFOS_BN_EPI", "auto")
     if mode not in ("auto", "off", "force"):
         raise ValueError("TFOS_BN_EPI must be auto, off or force, got "
@@ -1263,24 +1234,12 @@ class _BottleneckFn(torch.autograd.Function):
         ext = get_ext(required=True)
         N, Cin, H, W = x.shape
         C1, C2, C3 = w1.shape[0], w2.shape[0], w3.shape[0]
-
-        def as2d(t):
-            return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
-
-        def as4d(t2, h, w):
-            return t2.view(N, h, w, -1).permute(0, 3, 1, 2)
-
-        # packed bf16 weights: from the batched PackPlan when supplied
-        # (one kernel for the whole model per optimizer step), else inline
-        if packs is not None:
-            w1b = packs["w1b"].reshape(C1, Cin)
-            w9 = packs["w9"].reshape(C2, 9 * C1)
-            w3b = packs["w3b"].reshape(C3, C2)
-        else:
-            w1b = w1.view(C1, Cin).to(torch.bfloat16).contiguous()
-            w9 = w2.permute(0, 2, 3, 1).reshape(C2, 9 * C1) \
-                .to(torch.bfloat16).contiguous()
-            w3b = w3.view(C3, C2).to(torch.bfloat16).contiguous()
+        # packed bf16 weights, by PackPlan key: the plan's views when supplied
+        # (one kernel for the whole model per optimizer step), else each
+        # layout computed eagerly where it is first read
+        ctx.packs = packs
+        if packs is None:
+            packs = EagerPacks(w1, w2, w3, wd, stride)
         # TFOS_BN_EPI: a conv routed to its statistics-epilogue variant hands
         # the BN that follows the tile partials of its output (part, rows), and
         # that BN merges them instead of reading the tensor back; part is None
@@ -1307,24 +1266,23 @@ class _BottleneckFn(torch.autograd.Function):
             return ext.bn_fwd_train(t, res, g, b, rm, rv, momentum, eps, relu)
 
         OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-        t1, p1, n1 = gemm(as2d(x), w1b)
-        t1 = as4d(t1, H, W)
+        t1, p1, n1 = gemm(as2d(x), packs["w1b"].reshape(C1, Cin))
+        t1 = as4d(t1, N, H, W)
         a1, m1, r1, k1 = bn(t1, None, p1, n1, g1, b1, rm1, rv1, True)
-        t2, p2, n2 = conv(a1, w9, C2, 3, stride, 1, N * OH * OW)
+        t2, p2, n2 = conv(a1, packs["w9"].reshape(C2, 9 * C1), C2, 3, stride,
+                          1, N * OH * OW)
         a2, m2, r2, k2 = bn(t2, None, p2, n2, g2, b2, rm2, rv2, True)
         assert (OH, OW) == (t2.shape[2], t2.shape[3])
-        t3, p3, n3 = gemm(as2d(a2), w3b)
-        t3 = as4d(t3, OH, OW)
+        t3, p3, n3 = gemm(as2d(a2), packs["w3b"].reshape(C3, C2))
+        t3 = as4d(t3, N, OH, OW)
 
         if wd is not None:
-            wdb = packs["wdb"].reshape(C3, Cin) if packs is not None \
-                else wd.view(C3, Cin).to(torch.bfloat16).contiguous()
+            wdb = packs["wdb"].reshape(C3, Cin)
             if stride == 1:
                 td, pd, nd = gemm(as2d(x), wdb)
-                td = as4d(td, H, W)
+                td = as4d(td, N, H, W)
             else:
                 td, pd, nd = conv(x, wdb, C3, 1, stride, 0, N * OH * OW)
-            import os
             dual = os.environ.get("TFOS_BN_DUAL", "on") != "off" \
                 and ext.bn_dual_eligible(t3, td)
             if dual:
@@ -1354,7 +1312,6 @@ class _BottleneckFn(torch.autograd.Function):
                               w2, g2, t2, a2, m2, r2, k2,
                               w3, g3, t3, m3, r3, k3, y, wd, gd, *opt)
         ctx.meta = (stride, wd is not None, dual)
-        ctx.packs = packs
         return y
 
     @staticmethod
@@ -1364,21 +1321,20 @@ class _BottleneckFn(torch.autograd.Function):
          w3, g3, t3, m3, r3, k3, y, wd, gd, *opt) = ctx.saved_tensors
         stride, has_down, dual = ctx.meta
         packs = ctx.packs
+        if packs is None:       # from the saved weights, as forward's was
+            packs = EagerPacks(w1, w2, w3, wd, stride)
         N, Cin, H, W = x.shape
         C1, C2, C3 = w1.shape[0], w2.shape[0], w3.shape[0]
         OH, OW = t2.shape[2], t2.shape[3]
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-
-        def as2d(t):
-            return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
-
-        def as4d(t2d, h, w):
-            return t2d.view(N, h, w, -1).permute(0, 3, 1, 2)
+        dy = _cl_bf16(dy)
 
         def cl(t):
             return t.contiguous(memory_format=torch.channels_last)
+
+        def wrw(dyt, xt, w, k, s_):
+            # the fused block has never taken the round-1 conv_wrw kernel:
+            # under TFOS_WRW=mfma its weight gradients stay on the library
+            return _weight_grad(dyt, xt, w, k, s_, k // 2, round1=False)
 
         # block tail: bn3(+res+relu) backward -> dt3 plus the gated residual
         # gradient dres (doubles as the dx accumulation buffer below)
@@ -1392,21 +1348,10 @@ class _BottleneckFn(torch.autograd.Function):
                                              True, True)
         dt3 = cl(dt3)
 
-        def lib_wrw(dyt, xt, w4, s_, p_):
-            w4 = w4.to(torch.bfloat16).contiguous(
-                memory_format=torch.channels_last)
-            _, dw, _ = torch.ops.aten.convolution_backward(
-                dyt, xt, w4, None, [s_, s_], [p_, p_], [1, 1], False, [0, 0],
-                1, [False, True, False])
-            return dw
-
         # conv3 (1x1): dgrad + wrw
-        w3bT = packs["w3bT"].reshape(C2, C3) if packs is not None \
-            else w3.view(C3, C2).to(torch.bfloat16).t().contiguous()
-        da2 = cl(as4d(ext.gemm_bt(as2d(dt3), w3bT, True), OH, OW))
-        dw3 = ext.conv_wrw2(dt3, a2, 1, 1, 1, 0).view(C3, C2, 1, 1) \
-            if _use_wrw2(1, C2, C3) \
-            else lib_wrw(dt3, a2, w3.view(C3, C2, 1, 1), 1, 0)
+        da2 = cl(as4d(ext.gemm_bt(as2d(dt3), packs["w3bT"].reshape(C2, C3),
+                                  True), N, OH, OW))
+        dw3 = wrw(dt3, a2, w3, 1, 1)
 
         # bn2+relu backward
         dt2, dg2, db2 = ext.bn_bwd(t2, da2, a2, k2, g2, m2, r2, True, False)
@@ -1417,34 +1362,20 @@ class _BottleneckFn(torch.autograd.Function):
             da1 = torch.empty(N, C1, H, W, device=x.device,
                               dtype=torch.bfloat16) \
                 .contiguous(memory_format=torch.channels_last)
-            if packs is not None:
-                _conv_parity_packed(dt2, packs, "w9p", da1, 3, 1)
-            else:
-                wperm2 = w2.flip(2, 3).permute(1, 2, 3, 0) \
-                    .to(torch.bfloat16).contiguous()
-                _conv_parity(dt2, wperm2, da1, 3, 1)
+            _conv_parity_packed(dt2, packs, "w9p", da1, 3, 1)
         else:
-            w9p = packs["w9p"].reshape(C1, 9 * C2) if packs is not None \
-                else w2.flip(2, 3).permute(1, 2, 3, 0).reshape(C1, 9 * C2) \
-                .to(torch.bfloat16).contiguous()
-            da1 = ext.conv_mfma(dt2, w9p, C1, 3, 3, 1, 1, 1, H, W)
-        if _use_wrw2(3, C1, C2):
-            dw9 = ext.conv_wrw2(dt2, a1, 3, 3, stride, 1)
-            dw2 = dw9.view(C2, 3, 3, C1).permute(0, 3, 1, 2).contiguous()
-        else:
-            dw2 = lib_wrw(dt2, a1, w2, stride, 1)
+            da1 = ext.conv_mfma(dt2, packs["w9p"].reshape(C1, 9 * C2), C1,
+                                3, 3, 1, 1, 1, H, W)
+        dw2 = wrw(dt2, a1, w2, 3, stride)
 
         # bn1+relu backward
         dt1, dg1, db1 = ext.bn_bwd(t1, da1, a1, k1, g1, m1, r1, True, False)
         dt1 = cl(dt1)
 
         # conv1 (1x1) wrw
-        dw1 = ext.conv_wrw2(dt1, x, 1, 1, 1, 0).view(C1, Cin, 1, 1) \
-            if _use_wrw2(1, Cin, C1) \
-            else lib_wrw(dt1, x, w1.view(C1, Cin, 1, 1), 1, 0)
+        dw1 = wrw(dt1, x, w1, 1, 1)
 
-        w1bT = packs["w1bT"].reshape(Cin, C1) if packs is not None \
-            else w1.view(C1, Cin).to(torch.bfloat16).t().contiguous()
+        w1bT = packs["w1bT"].reshape(Cin, C1)
         if has_down:
             if not dual:
                 td, idn, md, rd = opt
@@ -1454,31 +1385,23 @@ class _BottleneckFn(torch.autograd.Function):
                                                        device=td.device),
                                            gd, md, rd, False, False)
             dtd = cl(dtd)
-            dwd = ext.conv_wrw2(dtd, x, 1, 1, stride, 0) \
-                .view(C3, Cin, 1, 1) if _use_wrw2(1, Cin, C3) \
-                else lib_wrw(dtd, x, wd.view(C3, Cin, 1, 1), stride, 0)
+            dwd = wrw(dtd, x, wd, 1, stride)
             # dx = conv1_dgrad, then downsample dgrad ACCUMULATES into it
-            dx2d = ext.gemm_bt(as2d(dt1), w1bT, True)
-            dx = cl(as4d(dx2d, H, W))
-            wdbT = packs["wdbT"].reshape(Cin, C3) if packs is not None \
-                else wd.view(C3, Cin).to(torch.bfloat16).t().contiguous()
+            dx = cl(as4d(ext.gemm_bt(as2d(dt1), w1bT, True), N, H, W))
+            wdbT = packs["wdbT"].reshape(Cin, C3)
             if stride == 1:
                 ext.gemm_bt_acc(as2d(dtd), wdbT, as2d(dx))
             else:
                 # even-even parity class only; odd pixels' contribution is 0
                 ext.conv_par(dtd, wdbT, dx, [0], [0], 0, True)
-            dwd = dwd.to(wd.dtype)
-            dgd_, dbd_ = dgd, dbd
         else:
             # dx = dres + conv1_dgrad — accumulate straight into dres
             dx = dres
             ext.gemm_bt_acc(as2d(dt1), w1bT, as2d(dx))
-            dwd = dgd_ = dbd_ = None
+            dwd = dgd = dbd = None
 
-        return (dx, dw1.to(w1.dtype), dg1, db1, None, None,
-                dw2.to(w2.dtype), dg2, db2, None, None,
-                dw3.to(w3.dtype), dg3, db3, None, None,
-                dwd, dgd_, dbd_, None, None,
+        return (dx, dw1, dg1, db1, None, None, dw2, dg2, db2, None, None,
+                dw3, dg3, db3, None, None, dwd, dgd, dbd, None, None,
                 None, None, None, None)
 
 
@@ -1507,10 +1430,7 @@ class _StemConvFn(torch.autograd.Function):
             .contiguous(memory_format=torch.channels_last)
         x4[:, :3, 3:H + 3, 3:W + 3] = x
         if w224 is None:
-            # w224[cout][r][s*4+c]: s<7, c<3 real else zero
-            w224 = torch.zeros(Cout, 7, 8, 4, dtype=torch.bfloat16,
-                               device=x.device)
-            w224[:, :, :7, :3] = weight.permute(0, 2, 3, 1).to(torch.bfloat16)
+            w224 = stem_w224(weight)
         y = ext.conv_stem(x4, w224.reshape(Cout, 224).contiguous(), Cout)
         ctx.save_for_backward(x4, weight)
         return y
@@ -1519,10 +1439,7 @@ class _StemConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         ext = get_ext(required=True)
         x4, weight = ctx.saved_tensors
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        dw224 = ext.conv_stem_wrw(dy, x4)          # [Cout, 224] fp32
+        dw224 = ext.conv_stem_wrw(_cl_bf16(dy), x4)  # [Cout, 224] fp32
         Cout = weight.shape[0]
         dw = dw224.view(Cout, 7, 8, 4)[:, :, :7, :3].permute(0, 3, 1, 2)
         return None, dw.contiguous().to(weight.dtype), None
@@ -1542,7 +1459,6 @@ class StemConv7x7(nn.Module):
                                 nonlinearity="relu")
 
     def forward(self, x):
-        import os
         if x.is_cuda and x.dtype == torch.bfloat16 and not x.requires_grad \
                 and os.environ.get("TFOS_STEM", "mfma") == "mfma" \
                 and get_ext(required=True) is not None:

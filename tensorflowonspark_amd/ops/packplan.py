@@ -12,7 +12,10 @@ them into one bf16 arena in one launch; the plan re-runs only when a parameter
 ``_version`` changes (i.e. once per optimizer step, not per micro-batch).
 """
 
+import functools
+import os
 import struct
+from collections.abc import Mapping
 
 import torch
 
@@ -99,35 +102,67 @@ class PackPlan:
         return True
 
 
+# ---------------------------------------------------------------------------
+# The weight layouts the kernels consume: each one as the eager torch form
+# (bf16, contiguous) and, right below it, as the PackPlan affine-gather spec
+# that produces the same bits from NCHW-contiguous fp32 parameter storage.
+# ---------------------------------------------------------------------------
+
+def rows(w):
+    """[Cout, Cin(,1,1)] -> bf16 [Cout, Cin] GEMM rows (cast only)."""
+    return w.reshape(w.shape[0], w.shape[1]).to(torch.bfloat16).contiguous()
+
+
 def _gemm_row_spec(plan, w):
-    """[Cout, Cin(,1,1)] fp32 -> bf16 [Cout, Cin] rows (cast only)."""
     co, ci = w.shape[0], w.shape[1]
     return plan.add(w, (co, ci), (ci, 1), 0)
 
 
+def rows_t(w):
+    """Transposed rows: bf16 [Cin, Cout]."""
+    return rows(w).t().contiguous()
+
+
 def _gemm_rowT_spec(plan, w):
-    """transposed rows: bf16 [Cin, Cout]."""
     co, ci = w.shape[0], w.shape[1]
     return plan.add(w, (ci, co), (1, ci), 0)
 
 
+def im2col(w):
+    """[C2, C1, k, k] -> [C2, k*k*C1], row = (r, s, c1): the forward weight
+    of a k x k conv ("w9") and the dgrad weight of a transposed conv."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1) \
+        .to(torch.bfloat16).contiguous()
+
+
 def _w9_spec(plan, w):
-    """[C2, C1, 3, 3] -> [C2, 3, 3, C1] (im2col fwd layout)."""
+    """im2col of a 3x3 filter, kept as [C2, 3, 3, C1]."""
     c2, c1 = w.shape[0], w.shape[1]
     return plan.add(w, (c2, 3, 3, c1), (9 * c1, 3, 1, 9), 0)
 
 
+def flipped(w):
+    """[C2, C1, k, k] -> [C1, k, k, C2] with out[c1][r][s][c2] =
+    w[c2][c1][k-1-r][k-1-s]: the backward-data weight of a conv ("w9p")
+    and the forward weight of a transposed conv."""
+    return w.flip(2, 3).permute(1, 2, 3, 0).to(torch.bfloat16).contiguous()
+
+
 def _w9p_spec(plan, w):
-    """[C2, C1, 3, 3] -> flipped/swapped [C1, 3, 3, C2] for backward-data:
-    out[ci][r][s][co] = w[co][ci][2-r][2-s] (negative strides + offset)."""
+    """flipped() of a 3x3 filter (negative strides + offset)."""
     c2, c1 = w.shape[0], w.shape[1]
     return plan.add(w, (c1, 3, 3, c2), (9, -3, -1, 9 * c1), 8)
 
 
+def parity_class(wperm, r_list, s_list):
+    """One stride-2 parity class of a flipped() weight: its taps
+    r_list x s_list (arithmetic, step 2), r-major, [C1, nr, ns, C2]."""
+    return wperm[:, r_list[0]::2, s_list[0]::2, :].contiguous()
+
+
 def _w9p_class_spec(plan, w, r_list, s_list):
-    """One stride-2 parity class: out[ci][ri][si][co] =
-    w[co][ci][2-r_list[ri]][2-s_list[si]]; r/s lists are arithmetic (step 2)
-    so the gather is affine."""
+    """parity_class(flipped(w)) of a 3x3 filter: out[ci][ri][si][co] =
+    w[co][ci][2-r_list[ri]][2-s_list[si]]."""
     c2, c1 = w.shape[0], w.shape[1]
     r0, s0 = r_list[0], s_list[0]
     rstep = (r_list[1] - r_list[0]) if len(r_list) > 1 else 1
@@ -137,9 +172,16 @@ def _w9p_class_spec(plan, w, r_list, s_list):
                     (9, -rstep * 3, -sstep, 9 * c1), soff)
 
 
-def _stem_spec(plan, w):
+def stem_w224(w):
     """[64, 3, 7, 7] -> zero-padded NHWC4 row layout [64, 7, 8, 4]:
     out[co][r][s][c] = w[co][c][r][s] (s<7, c<3; else 0)."""
+    out = torch.zeros(w.shape[0], 7, 8, 4, dtype=torch.bfloat16,
+                      device=w.device)
+    out[:, :, :7, :3] = w.permute(0, 2, 3, 1).to(torch.bfloat16)
+    return out
+
+
+def _stem_spec(plan, w):
     co = w.shape[0]
     return plan.add(w, (co, 7, 8, 4), (147, 7, 1, 49), 0,
                     valid=(co, 7, 7, 3))
@@ -156,6 +198,48 @@ def _class_taps(k, pp):
     return out
 
 
+def bottleneck_layouts(w1, w2, w3, wd, stride):
+    """The packed weights of one fused Bottleneck: key -> (eager form, spec,
+    weight, *extra arguments of both)."""
+    t = {"w1b": (rows, _gemm_row_spec, w1), "w9": (im2col, _w9_spec, w2),
+         "w3b": (rows, _gemm_row_spec, w3),
+         "w3bT": (rows_t, _gemm_rowT_spec, w3),
+         "w1bT": (rows_t, _gemm_rowT_spec, w1)}
+    if stride == 1:
+        t["w9p"] = (flipped, _w9p_spec, w2)
+    else:
+        wperm = functools.lru_cache(None)(flipped)  # one flip, four classes
+        for (ph, pw), (rl, sl) in _class_taps(3, 1).items():
+            t["w9p_{}{}".format(ph, pw)] = (
+                lambda w, rl, sl: parity_class(wperm(w), rl, sl),
+                _w9p_class_spec, w2, rl, sl)
+    if wd is not None:
+        t["wdb"] = (rows, _gemm_row_spec, wd)
+        t["wdbT"] = (rows_t, _gemm_rowT_spec, wd)
+    return t
+
+
+class EagerPacks(Mapping):
+    """The keys PackPlan attaches to a Bottleneck, each value its eager
+    layout, computed when first read (the block without PackPlan views)."""
+
+    def __init__(self, w1, w2, w3, wd, stride):
+        self._table = bottleneck_layouts(w1, w2, w3, wd, stride)
+        self._made = {}
+
+    def __getitem__(self, key):
+        if key not in self._made:
+            eager, _spec, w, *args = self._table[key]
+            self._made[key] = eager(w, *args)
+        return self._made[key]
+
+    def __iter__(self):
+        return iter(self._table)
+
+    def __len__(self):
+        return len(self._table)
+
+
 def build_resnet_plan(model, device):
     """Walk a ResNet's fused-eligible blocks + stem; returns (plan, attach)
     where attach() stores each block's packed views on the module."""
@@ -166,24 +250,10 @@ def build_resnet_plan(model, device):
     entries = []  # (module, {name: idx})
     for m in model.modules():
         if isinstance(m, Bottleneck) and getattr(m, "_block_fusable", False):
-            w1, w2, w3 = m.conv1.weight, m.conv2.weight, m.conv3.weight
-            e = {
-                "w1b": _gemm_row_spec(plan, w1),
-                "w9": _w9_spec(plan, w2),
-                "w3b": _gemm_row_spec(plan, w3),
-                "w3bT": _gemm_rowT_spec(plan, w3),
-                "w1bT": _gemm_rowT_spec(plan, w1),
-            }
-            if m.stride == 1:
-                e["w9p"] = _w9p_spec(plan, w2)
-            else:
-                for (ph, pw), (rl, sl) in _class_taps(3, 1).items():
-                    e["w9p_{}{}".format(ph, pw)] = _w9p_class_spec(
-                        plan, w2, rl, sl)
-            if m.downsample is not None:
-                wd = m.downsample[0].weight
-                e["wdb"] = _gemm_row_spec(plan, wd)
-                e["wdbT"] = _gemm_rowT_spec(plan, wd)
+            wd = m.downsample[0].weight if m.downsample is not None else None
+            e = {key: spec(plan, w, *args) for key, (_eager, spec, w, *args)
+                 in bottleneck_layouts(m.conv1.weight, m.conv2.weight,
+                                       m.conv3.weight, wd, m.stride).items()}
             entries.append((m, e))
         elif isinstance(m, StemConv7x7):
             entries.append((m, {"w224": _stem_spec(plan, m.weight)}))
@@ -200,7 +270,6 @@ def ensure_packed(model, x):
     any parameter version changed. Returns the packs availability flag."""
     if not (model.training and x.is_cuda and x.dtype == torch.bfloat16):
         return False
-    import os
     if os.environ.get("TFOS_PACK_PLAN", "on") == "off" \
             or os.environ.get("TFOS_FUSED_BLOCK", "on") == "off":
         return False
