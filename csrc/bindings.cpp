@@ -4,7 +4,10 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
+#include <c10/hip/HIPException.h>
 #include <climits>
+#include <map>
+#include <mutex>
 
 extern "C" {
 int tfosr_bn_fast_blocks(long, int, int, int);
@@ -107,6 +110,40 @@ namespace {
 
 hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
+}
+
+// The conv kernels redirect out-of-image taps to a small all-zero buffer
+// (every kernel takes it as const bf16_t* and only ever loads from it). One
+// buffer per device, created on first use and kept for the process: it is
+// zeroed with a blocking memset and a device synchronize before the pointer
+// is handed out, so no stream can read it early, and later calls cost
+// neither an allocation nor a fill launch.
+const void* zero_guard(const at::Tensor& like) {
+  constexpr size_t kGuardBytes = 256;  // kernels read at most 64 bf16
+  static std::mutex mu;
+  static std::map<int, void*> cache;
+  TORCH_CHECK(like.is_cuda(), "zero_guard: expected a GPU tensor");
+  const int dev = like.get_device();
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  C10_HIP_CHECK(hipStreamIsCapturing(cur_stream(), &cap));
+  TORCH_CHECK(cap == hipStreamCaptureStatusNone,
+              "the conv kernels' zero guard for device ", dev,
+              " is created on first use with a blocking fill, which a stream "
+              "capture does not allow: run one conv on this device before "
+              "capturing");
+  int prev = 0;
+  C10_HIP_CHECK(hipGetDevice(&prev));
+  C10_HIP_CHECK(hipSetDevice(dev));
+  void* p = nullptr;
+  C10_HIP_CHECK(hipMalloc(&p, kGuardBytes));
+  C10_HIP_CHECK(hipMemset(p, 0, kGuardBytes));
+  C10_HIP_CHECK(hipDeviceSynchronize());
+  C10_HIP_CHECK(hipSetDevice(prev));
+  cache.emplace(dev, p);
+  return p;
 }
 
 struct BNLayout {
@@ -1033,7 +1070,7 @@ static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
   auto y = at::empty({N, Cout, OH, OW},
                      x.options().dtype(out_f32 ? at::kFloat : at::kBFloat16),
                      at::MemoryFormat::ChannelsLast);
-  auto guard = at::zeros({64}, x.options());
+  const void* guard = zero_guard(x);
   if (stats && D == 1 && !out_f32) {
     TORCH_CHECK(x.is_cuda() && wk.device() == x.device(),
                 "conv_mfma_stats: x and wk must be on one GPU");
@@ -1041,12 +1078,12 @@ static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
     auto part = at::empty({(M + 255) / 256, 2, Cout},
                           x.options().dtype(at::kFloat));
     tfosr_conv_mfma_stats(x.data_ptr(), wk.contiguous().data_ptr(),
-                          guard.data_ptr(), y.data_ptr(),
+                          guard, y.data_ptr(),
                           part.data_ptr<float>(), N, H, W, Cin, Cout, OH, OW, S,
                           P, taps, fw, (int)fd, cur_stream());
     return {y, part};
   }
-  tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard.data_ptr(),
+  tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard,
                   y.data_ptr(), /*out_bf16=*/out_f32 ? 0 : 1, N, H, W, Cin,
                   Cout, OH, OW, S, P, taps, fw, D, 0, (int)fd, cur_stream());
   return {y, c10::nullopt};
@@ -1117,8 +1154,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     int OH = (H + 2 * P - 3) / S + 1, OW = (W + 2 * P - 3) / S + 1;
     auto y = at::empty({N, Cout, OH, OW}, x.options(),
                        at::MemoryFormat::ChannelsLast);
-    auto guard = at::zeros({64}, x.options());
-    tfosr_conv3x3(x.data_ptr(), w9.contiguous().data_ptr(), guard.data_ptr(),
+    const void* guard = zero_guard(x);
+    tfosr_conv3x3(x.data_ptr(), w9.contiguous().data_ptr(), guard,
                   y.data_ptr(), /*out_bf16=*/1, N, H, W, Cin, Cout, OH, OW,
                   S, P, cur_stream());
     return y;
@@ -1176,8 +1213,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     TORCH_CHECK(wk.size(1) == taps * Cin);
     long Cout = out.size(1), OH = out.size(2), OW = out.size(3);
     TORCH_CHECK(out.size(0) == N);
-    auto guard = at::zeros({64}, x.options());
-    tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard.data_ptr(),
+    const void* guard = zero_guard(x);
+    tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard,
                     out.data_ptr(), /*out_bf16=*/1, N, H, W, Cin, Cout, OH, OW,
                     S, P, taps, fw, D, 1, /*fd=*/1, cur_stream());
     return out;
@@ -1233,11 +1270,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     long M = (long)N * OH * OW;
     int split = tfosr_wrw2_split(Cout, Cin, M);
     long K = taps * (long)Cin;
+    // the split reduce indexes the workspace with 32-bit offsets
+    TORCH_CHECK((long)split * Cout * K < (1L << 32),
+                "conv_wrw2: the split workspace exceeds 2^32 elements");
     auto ws = at::empty({(long)split, (long)Cout * K},
                         x.options().dtype(at::kFloat));
     auto dW = at::empty({(long)Cout, K}, x.options().dtype(at::kFloat));
-    auto guard = at::zeros({64}, x.options());
-    tfosr_conv_wrw2(dy.data_ptr(), x.data_ptr(), guard.data_ptr(),
+    const void* guard = zero_guard(x);
+    tfosr_conv_wrw2(dy.data_ptr(), x.data_ptr(), guard,
                     ws.data_ptr<float>(), dW.data_ptr<float>(), N, H, W, Cin,
                     Cout, OH, OW, R, S_f, stride, P, split, (int)fd,
                     cur_stream());
@@ -1299,8 +1339,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     unsigned long pack = 0;
     for (long i = 0; i < ntaps; ++i)
       pack |= ((unsigned long)((taps_r[i] << 4) | taps_s[i])) << (i * 8);
-    auto guard = at::zeros({64}, x.options());
-    tfosr_conv_par(x.data_ptr(), wk.contiguous().data_ptr(), guard.data_ptr(),
+    const void* guard = zero_guard(x);
+    tfosr_conv_par(x.data_ptr(), wk.contiguous().data_ptr(), guard,
                    out.data_ptr(), N, H, W, Cin, (int)Cout, (int)OHs,
                    (int)OWs, (int)P, (int)ntaps, pack, (int)oh0, (int)ow0,
                    (int)OWr, OHr * OWr, accum ? 1 : 0, cur_stream());
@@ -1320,9 +1360,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     int OH = (Hp - 7) / 2 + 1, OW = (Wp - 7) / 2 + 1;
     auto y = at::empty({N, Cout, OH, OW}, x4.options(),
                        at::MemoryFormat::ChannelsLast);
-    auto guard = at::zeros({64}, x4.options());
+    const void* guard = zero_guard(x4);
     tfosr_conv_stem(x4.data_ptr(), w224.contiguous().data_ptr(),
-                    guard.data_ptr(), y.data_ptr(), N, Hp, Wp, Cout, OH, OW,
+                    guard, y.data_ptr(), N, Hp, Wp, Cout, OH, OW,
                     cur_stream());
     return y;
   });
@@ -1338,11 +1378,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     long M = (long)N * OH * OW;
     int split = tfosr_wrw2_split(Cout, 32, M);
     long K = 7L * 32;
+    TORCH_CHECK((long)split * Cout * K < (1L << 32),
+                "conv_stem_wrw: the split workspace exceeds 2^32 elements");
     auto ws = at::empty({(long)split, (long)Cout * K},
                         x4.options().dtype(at::kFloat));
     auto dW = at::empty({(long)Cout, K}, x4.options().dtype(at::kFloat));
-    auto guard = at::zeros({64}, x4.options());
-    tfosr_conv_wrw2(dy.data_ptr(), x4.data_ptr(), guard.data_ptr(),
+    const void* guard = zero_guard(x4);
+    tfosr_conv_wrw2(dy.data_ptr(), x4.data_ptr(), guard,
                     ws.data_ptr<float>(), dW.data_ptr<float>(), N, Hp, Wp,
                     /*Cin=*/32, Cout, OH, OW, /*R=*/7, /*S_f=*/1,
                     /*stride=*/2, /*P=*/0, split, /*fd=*/1, cur_stream());

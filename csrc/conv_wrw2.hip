@@ -45,8 +45,19 @@ __device__ __forceinline__ unsigned wrw_div(unsigned m, unsigned long magic) {
   return (unsigned)(((unsigned long)m * magic) >> 40);
 }
 
-// TAPS = R*S (1 or 9); regions = TAPS+1 (dy first), each 32m x 64c
-template <int TAPS, int DEPTH>
+// TAPS = R*S; regions = TAPS+1 (dy first): dy MSTEP m x 64 c, x MSTEP m x
+// CIN_T c each.
+//
+// CIN_T = 64 is the layout described above. CIN_T = 32 serves the stem,
+// whose virtual Cin is 32 (8 px x 4 ch per tap row): in the 64-wide tile
+// waves 2 and 3 multiplied zeros and half of every K-step's x chunks were
+// staged from a clamped address only to be zeroed again. With 32-wide x
+// regions the K-step grows to 64 pixels (two MFMA k-halves per barrier, as
+// in wrw_gemm_tn_kernel) so a slot is still a whole number of 256-chunk
+// rounds and every chunk of a thread still holds one pixel; the waves split
+// 2 x 2: wave w owns x block (w & 1) and the 32 couts of half (w >> 1) —
+// 14 MFMAs per 9 fragments, all four waves on real data.
+template <int TAPS, int DEPTH, int CIN_T = 64>
 __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
     const bf16_t* __restrict__ dy, const bf16_t* __restrict__ X,
     const bf16_t* __restrict__ guard, float* __restrict__ ws,
@@ -54,10 +65,17 @@ __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
     int stride, int P, int pixst, int steps_per_wg, long M,
     unsigned long magicOW, unsigned long magicOHOW, int ntn, int split,
     int fd) {
-  constexpr int REG = TAPS + 1;
-  constexpr int REGB = 32 * 64 * 2;           // 4 KB per region
-  constexpr int SLOT = REG * REGB;
-  constexpr int CPT = REG * 256 / 256;        // chunks per thread per slot
+  static_assert(CIN_T == 64 || CIN_T == 32, "x tile is 64 or 32 channels");
+  constexpr int MSTEP = CIN_T == 64 ? 32 : 64;  // pixels per K-step
+  constexpr int MH = MSTEP / 32;                // MFMA k-halves per K-step
+  constexpr int BLKB = MSTEP * 16 * 2;          // one [MSTEP m][16 c] block
+  constexpr int DYCH = MSTEP * 8;               // 16 B chunks: dy region
+  constexpr int XCH = MSTEP * CIN_T / 8;        //              x region
+  constexpr int REGB_DY = DYCH * 16, REGB_X = XCH * 16;
+  constexpr int SLOT = REGB_DY + TAPS * REGB_X;
+  static_assert((DYCH + TAPS * XCH) % 256 == 0, "whole rounds of 256 chunks");
+  constexpr int CPT = (DYCH + TAPS * XCH) / 256;  // chunks per thread per slot
+  constexpr int NCO = CIN_T == 64 ? 4 : 2;      // 16-cout blocks per wave
   __shared__ char lds[DEPTH * SLOT];
   AS3 char* lds3 = (AS3 char*)lds;
 
@@ -71,31 +89,35 @@ __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
   const int tile = wgid / split;       // output tile (cout x cin blocks)
   const int sp = wgid - tile * split;  // split-M slice
   const int cout0 = (tile / ntn) * 64;
-  const int cin0 = (tile % ntn) * 64;
+  const int cin0 = (tile % ntn) * CIN_T;
 
-  const long m_begin = (long)sp * steps_per_wg * 32;
+  const long m_begin = (long)sp * steps_per_wg * MSTEP;
   const int t = threadIdx.x;
   const int lane = t & 63;
-  const int wc = t >> 6;               // wave = 0..3: its 16-cin block
+  // wave = 0..3: its 16-cin block and its first 16-cout block
+  const int wc = CIN_T == 64 ? t >> 6 : (t >> 6) & 1;
+  const int co0 = CIN_T == 64 ? 0 : (t >> 7) * NCO;
 
   // global_load_lds writes lane-linearly from the wave base, so the LDS
   // destination is the plain linear chunk index; the (region, block, m, h)
   // the chunk HOLDS is decoded from that index instead. Every chunk of a
-  // thread holds the SAME pixel m ((t>>1)&31 — 256 = 0 mod 64), so the pixel
+  // thread holds the SAME pixel m ((t>>1)&(MSTEP-1) — 256 = 0 mod 2*MSTEP,
+  // and both region sizes are multiples of 256), so the pixel
   // decode (magic divisions) hoists to once per thread per k-step: VALUBusy
   // measured 42% before this hoist, the dominant pipe.
-  const int mloc = (t >> 1) & 31;
+  const int mloc = (t >> 1) & (MSTEP - 1);
   int ch_isdy[CPT], ch_r[CPT], ch_s[CPT], ch_ldsoff[CPT];
   long ch_coff[CPT];
   #pragma unroll
   for (int u = 0; u < CPT; ++u) {
     int q = t + u * 256;               // linear 16 B chunk index
-    int region = q >> 8;
+    int region = q < DYCH ? 0 : 1 + (q - DYCH) / XCH;
+    int qq = q < DYCH ? q : (q - DYCH) % XCH;  // chunk within the region
     // bank stagger: the 8-channel half stored at physical slot (q&1) is the
     // logical half flipped by bit3 of m — otherwise the four kslot groups of
     // a transpose-read land on identical banks (4-way conflict, measured
     // ratio 2.0 in SQ_LDS_BANK_CONFLICT)
-    int cb = (q >> 6) & 3, h = (q & 1) ^ ((q >> 4) & 1);
+    int cb = qq / (MSTEP * 2), h = (q & 1) ^ ((q >> 4) & 1);
     int tap = region - 1;
     ch_isdy[u] = region == 0;
     ch_r[u] = region ? (tap / FW) * fd - P : 0;  // fd: filter dilation
@@ -154,26 +176,28 @@ __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
     }
   };
 
-  // accumulators: 4 cout blocks x TAPS tiles of 16x16 (144 VGPRs at TAPS=9)
-  f32x4 acc[4][TAPS];
+  // accumulators: NCO cout blocks x TAPS tiles of 16x16 (144 VGPRs at
+  // TAPS=9, CIN_T=64)
+  f32x4 acc[NCO][TAPS];
   #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < NCO; ++i)
     #pragma unroll
     for (int j = 0; j < TAPS; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  long nkt = (M - m_begin + 31) / 32;
+  long nkt = (M - m_begin + MSTEP - 1) / MSTEP;
   if (nkt > steps_per_wg) nkt = steps_per_wg;
   if (nkt <= 0) nkt = 0;
 
-  // per-lane transpose-read address into a row-major [32m][16c] block
-  // (bytes); the t=1 half (m += 4) sits +128 B further
+  // per-lane transpose-read address into 32 rows of a row-major
+  // [MSTEP m][16c] block (bytes); the t=1 half (m += 4) sits +128 B
+  // further, the second k-half (m += 32) +1 KB
   const int lbase =
       ((((lane >> 4) * 8 + ((lane & 15) >> 2)) * 16) +
        ((lane & 3) ^ (((lane >> 4) & 1) << 1)) * 4) * 2;
 
-  auto trread8 = [&](AS3 char* region, int blk) -> bf16x8 {
+  auto trread8 = [&](AS3 char* region, int blk, int mh) -> bf16x8 {
     AS3 s16x4* p =
-        (AS3 s16x4*)(region + blk * 1024 + lbase);
+        (AS3 s16x4*)(region + blk * BLKB + mh * 1024 + lbase);
     s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(p);
     s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
         (AS3 s16x4*)((AS3 char*)p + 128));
@@ -185,13 +209,14 @@ __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
 
   #pragma unroll
   for (int pf = 0; pf < DEPTH - 1; ++pf)
-    if (pf < nkt) stage(pf, m_begin + (long)pf * 32);
+    if (pf < nkt) stage(pf, m_begin + (long)pf * MSTEP);
   // after staging slot kt+DEPTH-1, at most (DEPTH-1) newer slots in flight
   constexpr int INFLIGHT = (DEPTH - 1) * CPT;
 
   for (long kt = 0; kt < nkt; ++kt) {
     if (kt + DEPTH - 1 < nkt) {
-      stage((int)((kt + DEPTH - 1) % DEPTH), m_begin + (kt + DEPTH - 1) * 32);
+      stage((int)((kt + DEPTH - 1) % DEPTH),
+            m_begin + (kt + DEPTH - 1) * MSTEP);
       asm volatile("s_waitcnt vmcnt(%0)" ::"i"(INFLIGHT) : "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -202,23 +227,26 @@ __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
     __syncthreads();
 
     AS3 char* slot = lds3 + (kt % DEPTH) * SLOT;
-    // issue every fragment read up front so the MFMA chain never serially
-    // waits on LDS latency (1-2 waves/SIMD can't hide it otherwise)
-    bf16x8 afrag[4], bfrag[TAPS];
     #pragma unroll
-    for (int co = 0; co < 4; ++co)
-      afrag[co] = trread8(slot, co);
-    #pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap)
-      bfrag[tap] = trread8(slot + (tap + 1) * REGB, wc);
-    __builtin_amdgcn_s_setprio(1);
-    #pragma unroll
-    for (int tap = 0; tap < TAPS; ++tap)
+    for (int mh = 0; mh < MH; ++mh) {
+      // issue every fragment read up front so the MFMA chain never serially
+      // waits on LDS latency (1-2 waves/SIMD can't hide it otherwise)
+      bf16x8 afrag[NCO], bfrag[TAPS];
       #pragma unroll
-      for (int co = 0; co < 4; ++co)
-        acc[co][tap] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-            afrag[co], bfrag[tap], acc[co][tap], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
+      for (int co = 0; co < NCO; ++co)
+        afrag[co] = trread8(slot, co0 + co, mh);
+      #pragma unroll
+      for (int tap = 0; tap < TAPS; ++tap)
+        bfrag[tap] = trread8(slot + REGB_DY + tap * REGB_X, wc, mh);
+      __builtin_amdgcn_s_setprio(1);
+      #pragma unroll
+      for (int tap = 0; tap < TAPS; ++tap)
+        #pragma unroll
+        for (int co = 0; co < NCO; ++co)
+          acc[co][tap] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              afrag[co], bfrag[tap], acc[co][tap], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+    }
     // drain LDS reads before the barrier: the compiler may sink the mfma
     // consumers (and their lgkm waits) past __syncthreads, leaving tr-reads
     // in flight while the next iteration's staging overwrites the slot
@@ -234,8 +262,8 @@ __global__ __launch_bounds__(256, 1) void conv_wrw2_kernel(
   const int cin_g = cin0 + wc * 16 + ccol;
   if (cin_g < Cin) {
     #pragma unroll
-    for (int co = 0; co < 4; ++co) {
-      int cout_g0 = cout0 + co * 16 + crow0;
+    for (int co = 0; co < NCO; ++co) {
+      int cout_g0 = cout0 + (co0 + co) * 16 + crow0;
       #pragma unroll
       for (int r = 0; r < 4; ++r) {
         int cout_g = cout_g0 + r;
@@ -437,14 +465,77 @@ __global__ __launch_bounds__(256, 1) void wrw_gemm_tn_kernel(
   }
 }
 
-// dW[i] = sum over split slices of ws[s][i]
-__global__ void wrw_reduce_kernel(const float* __restrict__ ws,
-                                  float* __restrict__ dW, long n, int split) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float acc = 0.f;
-  for (int s = 0; s < split; ++s) acc += ws[(long)s * n + i];
-  dW[i] = acc;
+// Split-M reduce: dst[c][i] = sum of src rows [c*chunk, min((c+1)*chunk, rows))
+// at column i. A block is 64 consecutive VEC-wide columns x 4 slice groups
+// (one wave per group, so a wave reads one contiguous run of a row); thread
+// (col, g) sums rows g, g+4, ... of its chunk with RED_U independent loads in
+// flight, and the four groups meet through LDS in the order 0,1,2,3. No
+// atomics: the summation tree depends on (rows, chunk) alone. The serial
+// one-thread-per-element loop this replaces took 308 us whatever the size
+// (1024 dependent-in-order loads per thread, 0.5 TB/s).
+//
+// src and dst may be the same buffer (level 1 writes chunk c's partial over
+// row c*chunk of the workspace): a block reads only its own chunk's rows at
+// its own columns and stores after the barrier, so neither is __restrict__.
+// Offsets are 32-bit: the launcher checks rows * row stride < 2^32.
+constexpr int RED_COLS = 64, RED_GROUPS = 4, RED_U = 4, RED_CHUNK = 64;
+
+template <int VEC>
+__global__ __launch_bounds__(RED_COLS * RED_GROUPS) void wrw_reduce_kernel(
+    const float* src, float* dst, unsigned ncol, int rows, int chunk,
+    unsigned src_row, unsigned dst_row) {
+  typedef float vec_t __attribute__((ext_vector_type(VEC)));
+  __shared__ vec_t part[RED_GROUPS - 1][RED_COLS];
+  const int lane = threadIdx.x & (RED_COLS - 1);
+  const int g = threadIdx.x / RED_COLS;
+  const unsigned col = blockIdx.x * RED_COLS + lane;
+  const bool live = col < ncol;
+  const int s0 = blockIdx.y * chunk;
+  const int s1 = min(s0 + chunk, rows);
+  const vec_t zero = {};
+  vec_t acc = zero;
+  if (live) {
+    const vec_t* p = (const vec_t*)src + col;   // row stride is a multiple
+    for (int s = s0 + g; s < s1; s += RED_GROUPS * RED_U) {  // of VEC
+      vec_t v[RED_U];
+      #pragma unroll
+      for (int u = 0; u < RED_U; ++u) {
+        const int su = s + u * RED_GROUPS;
+        v[u] = su < s1 ? p[(unsigned)su * (src_row / VEC)] : zero;
+      }
+      #pragma unroll
+      for (int u = 0; u < RED_U; ++u) acc += v[u];
+    }
+  }
+  if (g > 0) part[g - 1][lane] = acc;
+  __syncthreads();
+  if (g == 0 && live) {
+    #pragma unroll
+    for (int k = 0; k < RED_GROUPS - 1; ++k) acc += part[k][lane];
+    ((vec_t*)dst)[blockIdx.y * (dst_row / VEC) + col] = acc;
+  }
+}
+
+// ws [split][n] -> dW [n]. Up to RED_CHUNK slices go in one level; above
+// that, level 1 leaves one partial row per chunk in the workspace itself and
+// level 2 sums those rows (at most 16 of them for split <= 1024).
+template <int VEC>
+static void wrw_reduce_launch(float* ws, float* dW, long n, int split,
+                              hipStream_t s) {
+  const unsigned ncol = (unsigned)(n / VEC);
+  const unsigned cb = (ncol + RED_COLS - 1) / RED_COLS;
+  dim3 block(RED_COLS * RED_GROUPS);
+  if (split <= RED_CHUNK) {
+    hipLaunchKernelGGL((wrw_reduce_kernel<VEC>), dim3(cb, 1), block, 0, s, ws,
+                       dW, ncol, split, split, (unsigned)n, 0u);
+    return;
+  }
+  const int nchunk = (split + RED_CHUNK - 1) / RED_CHUNK;
+  hipLaunchKernelGGL((wrw_reduce_kernel<VEC>), dim3(cb, nchunk), block, 0, s,
+                     ws, ws, ncol, split, RED_CHUNK, (unsigned)n,
+                     (unsigned)(RED_CHUNK * n));
+  hipLaunchKernelGGL((wrw_reduce_kernel<VEC>), dim3(cb, 1), block, 0, s, ws,
+                     dW, ncol, nchunk, nchunk, (unsigned)(RED_CHUNK * n), 0u);
 }
 
 extern "C" {
@@ -474,6 +565,10 @@ void tfosr_conv_wrw2(const void* dy, const void* x, const void* guard,
     ntn = (Cin + 127) / 128;
     ntiles = ((Cout + 127) / 128) * ntn;
     steps = (M + 63) / 64;
+  } else if (taps == 7) {  // stem: 64x32 tiles, 64-pixel steps
+    ntn = (Cin + 31) / 32;
+    ntiles = ((Cout + 63) / 64) * ntn;
+    steps = (M + 63) / 64;
   }
   const int spw = (int)((steps + split - 1) / split);
   dim3 grid(ntiles * split), block(256);
@@ -484,7 +579,7 @@ void tfosr_conv_wrw2(const void* dy, const void* x, const void* guard,
                        S_f, stride, P, Cin, spw, M, magicOW, magicOHOW, ntn,
                        split, fd);
   else if (taps == 7)  // stem wrw over the NHWC4 padded view (pixstride 4)
-    hipLaunchKernelGGL((conv_wrw2_kernel<7, 2>), grid, block, 0, s,
+    hipLaunchKernelGGL((conv_wrw2_kernel<7, 2, 32>), grid, block, 0, s,
                        (const bf16_t*)dy, (const bf16_t*)x,
                        (const bf16_t*)guard, ws, N, H, W, Cin, Cout, OH, OW,
                        S_f, stride, P, 4, spw, M, magicOW, magicOHOW, ntn,
@@ -495,8 +590,10 @@ void tfosr_conv_wrw2(const void* dy, const void* x, const void* guard,
                        (const bf16_t*)guard, ws, N, H, W, Cin, Cout, OH, OW,
                        stride, spw, M, magicOW, magicOHOW, ntn, split);
   const long n = (long)Cout * taps * Cin;
-  dim3 rg((n + 255) / 256), rb(256);
-  hipLaunchKernelGGL(wrw_reduce_kernel, rg, rb, 0, s, ws, dW, n, split);
+  if (n % 4 == 0)
+    wrw_reduce_launch<4>(ws, dW, n, split, s);
+  else
+    wrw_reduce_launch<1>(ws, dW, n, split, s);
 }
 
 }  // extern "C"

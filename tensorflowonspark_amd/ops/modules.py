@@ -22,6 +22,23 @@ def _cl_bf16(t):
     return t.contiguous(memory_format=torch.channels_last).to(torch.bfloat16)
 
 
+def _cl_alloc(shape, device, dtype=torch.bfloat16, zero=False):
+    """A fresh tensor of ``shape`` that is channels_last from birth.
+
+    ``torch.empty(shape).contiguous(memory_format=torch.channels_last)``
+    allocates an NCHW tensor, then a second one, and runs a strided permuting
+    copy of uninitialised memory between them: a whole-tensor read and write
+    per call. The strides here are the ones that expression ends with: where
+    NCHW memory already is channels_last-contiguous (one channel, or a 1x1
+    image) it kept the NCHW strides, and so does this."""
+    shape = tuple(shape)
+    nchw_is_cl = len(shape) == 4 and (shape[1] == 1 or shape[2:] == (1, 1))
+    t = torch.empty(shape, device=device, dtype=dtype,
+                    memory_format=torch.contiguous_format if nchw_is_cl
+                    else torch.channels_last)
+    return t.zero_() if zero else t
+
+
 def as2d(t):
     """channels_last [N, C, H, W] viewed as the [N*H*W, C] GEMM operand."""
     return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
@@ -519,8 +536,7 @@ class _Conv1x1S2Fn(torch.autograd.Function):
         dy = _cl_bf16(dy)
         # dx[h,w] = (h,w even) ? dy[h/2,w/2] @ W : 0 — only the even-even
         # parity class has a tap; zero-fill and launch just that class
-        dx = torch.zeros(x.shape, device=x.device, dtype=torch.bfloat16) \
-            .contiguous(memory_format=torch.channels_last)
+        dx = _cl_alloc(x.shape, x.device, zero=True)
         _conv_parity(dy, rows_t(weight).view(Cin, 1, 1, Cout), dx, 1, 0)
         return dx, _weight_grad(dy, x, weight, 1, 2, 0)
 
@@ -629,8 +645,7 @@ class _Conv3x3Fn(torch.autograd.Function):
         dy = _cl_bf16(dy)
         wperm = flipped(weight)
         if S == 2:
-            dx = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16) \
-                .contiguous(memory_format=torch.channels_last)
+            dx = _cl_alloc(x.shape, x.device)
             _conv_parity(dy, wperm, dx, 3, 1)
         else:
             dx = get_ext(required=True).conv_mfma(
@@ -914,9 +929,7 @@ class _ConvT2dFn(torch.autograd.Function):
         H, W = x.shape[2], x.shape[3]
         OH = (H - 1) * stride - 2 * padding + KH + output_padding
         OW = (W - 1) * stride - 2 * padding + KW + output_padding
-        y = torch.empty(x.shape[0], Cout, OH, OW, device=x.device,
-                        dtype=torch.bfloat16) \
-            .contiguous(memory_format=torch.channels_last)
+        y = _cl_alloc((x.shape[0], Cout, OH, OW), x.device)
         if KH % 2 or output_padding:  # some classes empty -> zero base
             y.zero_()
         _conv_parity(x, wperm, y, KH, KH - 1 - padding)
@@ -1359,9 +1372,7 @@ class _BottleneckFn(torch.autograd.Function):
 
         # conv2 (3x3, stride s): dgrad (parity-decomposed for s2) + wrw
         if stride == 2:
-            da1 = torch.empty(N, C1, H, W, device=x.device,
-                              dtype=torch.bfloat16) \
-                .contiguous(memory_format=torch.channels_last)
+            da1 = _cl_alloc((N, C1, H, W), x.device)
             _conv_parity_packed(dt2, packs, "w9p", da1, 3, 1)
         else:
             da1 = ext.conv_mfma(dt2, packs["w9p"].reshape(C1, 9 * C2), C1,
@@ -1425,9 +1436,7 @@ class _StemConvFn(torch.autograd.Function):
         ext = get_ext(required=True)
         N, _, H, W = x.shape
         Cout = weight.shape[0]
-        x4 = torch.zeros(N, 4, H + 6, W + 6, dtype=torch.bfloat16,
-                         device=x.device) \
-            .contiguous(memory_format=torch.channels_last)
+        x4 = _cl_alloc((N, 4, H + 6, W + 6), x.device, zero=True)
         x4[:, :3, 3:H + 3, 3:W + 3] = x
         if w224 is None:
             w224 = stem_w224(weight)

@@ -5,6 +5,7 @@ Covers the ResNet-50 stride-2 shapes and the U-Net decoder transposed convs
 (VERDICT r01 item 1/7). Run on a GPU box:
     python tools/conv_bench.py [--batch 1024]
     python tools/conv_bench.py --atrous [--batch 32] [--rounds 9]
+    python tools/conv_bench.py --wrwtail --parent-ext OLD/tfosr_hip_ops_parent.so
 """
 
 import argparse
@@ -58,6 +59,12 @@ def main():
     ap.add_argument("--wrw", action="store_true")
     ap.add_argument("--atrous", action="store_true",
                     help="DeepLabV3 dilated 3x3 shapes, in-tree vs library")
+    ap.add_argument("--wrwtail", action="store_true",
+                    help="split-M reduce and stem wrw: this tree's extension "
+                         "against another build of it (--parent-ext)")
+    ap.add_argument("--parent-ext", default=None,
+                    help="extension of the commit to compare against, built under "
+                         "a module name of its own (see load_ext_from)")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--json", default=None,
@@ -65,6 +72,10 @@ def main():
     args = ap.parse_args()
     if args.wrw:
         bench_wrw(args.batch)
+        return
+    if args.wrwtail:
+        bench_wrwtail(args.batch, args.parent_ext, max(args.rounds, 7),
+                      args.iters, args.json)
         return
     if args.atrous:
         bench_atrous(32 if args.batch == 1024 else args.batch, args.rounds,
@@ -148,10 +159,11 @@ ATROUS_SHAPES = [(512, 512, 32, 2), (2048, 256, 32, 12), (2048, 256, 32, 24),
                  (2048, 256, 32, 36)]
 
 
-def ab_median(sides, rounds, iters):
+def ab_median(sides, rounds, iters, spread=None):
     """Median ms per call of each side. The sides alternate inside every
     round (one process, one device), each timed with device events around
-    ``iters`` back-to-back calls, after a warm-up of every side."""
+    ``iters`` back-to-back calls, after a warm-up of every side. ``spread``
+    (a dict) receives max - min over the rounds of each side."""
     for fn in sides.values():
         for _ in range(3):
             fn()
@@ -167,6 +179,8 @@ def ab_median(sides, rounds, iters):
             e1.record()
             e1.synchronize()
             times[k].append(e0.elapsed_time(e1) / iters)
+    if spread is not None:
+        spread.update({k: max(v) - min(v) for k, v in times.items()})
     return {k: sorted(v)[len(v) // 2] for k, v in times.items()}
 
 
@@ -255,6 +269,87 @@ def bench_atrous(batch=32, rounds=9, iters=5, json_path=None):
             print(tag + ": " + cells, flush=True)
             rows.append(dict(direction=direction, cin=cin, cout=cout, hw=hw,
                              fd=fd, batch=N, flops=flops, ms=med))
+    if json_path:
+        os.makedirs(os.path.dirname(os.path.abspath(json_path)),
+                    exist_ok=True)
+        with open(json_path, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+def load_ext_from(path):
+    """Another build of the extension, next to the tree's own, in this
+    process. pybind11 hands out one module per module NAME, so the other
+    build's bindings.cpp is compiled with -DTORCH_EXTENSION_NAME=<stem of its
+    file name> (say tfosr_hip_ops_parent.so); its extern "C" launchers stay
+    its own, extension modules being loaded RTLD_LOCAL."""
+    import importlib.util
+    from tensorflowonspark_amd.ops import get_ext
+    name = os.path.basename(path).split(".")[0]
+    spec = importlib.util.spec_from_file_location(name, path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    if mod is get_ext(required=True):
+        raise RuntimeError(
+            "{} loaded as the tree's own extension: build it under another "
+            "module name (-DTORCH_EXTENSION_NAME)".format(path))
+    return mod
+
+
+def bench_wrwtail(batch=1024, parent_ext=None, rounds=7, iters=5,
+                  json_path=None):
+    """The two in-tree weight gradients of the ResNet-50 step end to end
+    (kernel + split-M reduce): conv_wrw2 64->64 3x3 @56 and conv_stem_wrw,
+    this tree's extension against --parent-ext, alternating. Next to them a
+    plain device copy of each split workspace's bytes (split x n fp32): what
+    a reduce at copy bandwidth would cost. The reduce kernels on their own
+    are read from a kernel trace of this same run."""
+    import json
+    from tensorflowonspark_amd.ops import get_ext
+    new = get_ext(required=True)
+    exts = {"new": new}
+    if parent_ext:
+        exts = {"parent": load_ext_from(parent_ext), "new": new}
+    bf16 = torch.bfloat16
+    torch.manual_seed(0)
+    N = batch
+
+    def cl(t):
+        return t.contiguous(memory_format=torch.channels_last)
+    x = cl((torch.randn(N, 64, 56, 56, device="cuda") / 4).to(bf16))
+    dy = cl((torch.randn(N, 64, 56, 56, device="cuda") / 4).to(bf16))
+    x4 = cl((torch.randn(N, 4, 230, 230, device="cuda") / 4).to(bf16))
+    dys = cl((torch.randn(N, 64, 112, 112, device="cuda") / 4).to(bf16))
+    rows = []
+    plan = [
+        ("conv_wrw2 64->64 3x3 @56", 64 * 9 * 64, N * 56 * 56,
+         lambda e: (lambda: e.conv_wrw2(dy, x, 3, 3, 1, 1))),
+        ("conv_stem_wrw @224", 64 * 224, N * 112 * 112,
+         lambda e: (lambda: e.conv_stem_wrw(dys, x4))),
+    ]
+    for tag, n, M, call in plan:
+        split = 1024                      # tfosr_wrw2_split of one 64x64 tile
+        while split * 8 > (M + 31) // 32 and split > 1:
+            split //= 2
+        src = torch.empty(split * n, device="cuda")
+        dst = torch.empty_like(src)
+        sides = {k: call(e) for k, e in exts.items()}
+        sides["copy"] = lambda: dst.copy_(src)
+        same = {k: fn().clone() for k, fn in sides.items() if k != "copy"}
+        if "parent" in same:
+            d = (same["new"].double() - same["parent"].double()).abs()
+            print("{}: new vs parent max |d| {:.3e} on max |dW| {:.3e}".format(
+                tag, d.max().item(), same["parent"].abs().max().item()))
+        spread = {}
+        med = ab_median(sides, rounds, iters, spread)
+        mb = split * n * 4 / 1e6
+        cells = "  ".join("{} {:.4f} ms (spread {:.4f})".format(
+            k, v, spread[k]) for k, v in med.items())
+        print("{} b{}: split {} x n {} = {:.0f} MB fp32 | {} | copy moves "
+              "{:.0f} GB/s read+write".format(
+                  tag, N, split, n, mb, cells, 2 * mb / med["copy"]),
+              flush=True)
+        rows.append(dict(tag=tag, batch=N, split=split, n=n, ws_mb=mb,
+                         ms=med, spread=spread))
     if json_path:
         os.makedirs(os.path.dirname(os.path.abspath(json_path)),
                     exist_ok=True)
