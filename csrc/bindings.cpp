@@ -67,6 +67,14 @@ void tfosr_maxpool_fwd(const void*, void*, unsigned char*, int, int, int, int,
                        int, int, int, int, int, int, hipStream_t);
 void tfosr_maxpool_bwd(const void*, const unsigned char*, void*, int, int, int,
                        int, int, int, int, int, int, int, hipStream_t);
+void tfosr_dwconv3x3_info(int*, int*, int*, int*, int*, int*, int*);
+void tfosr_dwconv3x3_wrw_plan(long, int, int*, int*, int*, int*, long*);
+void tfosr_dwconv3x3_fwd(const void*, const float*, void*, int, int, int, int,
+                         int, int, int, int, hipStream_t);
+void tfosr_dwconv3x3_dgrad(const void*, const float*, void*, int, int, int, int,
+                           int, int, int, int, hipStream_t);
+void tfosr_dwconv3x3_wrw(const void*, const void*, float*, float*, int, int,
+                         int, int, int, int, int, int, hipStream_t);
 void tfosr_conv3x3(const void*, const void*, const void*, void*, int, int, int,
                    int, int, int, int, int, int, int, hipStream_t);
 void tfosr_conv_mfma(const void*, const void*, const void*, void*, int, int,
@@ -1022,7 +1030,7 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 7
+#define TFOSR_API_VERSION 8
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
@@ -1087,6 +1095,129 @@ static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
                   y.data_ptr(), /*out_bf16=*/out_f32 ? 0 : 1, N, H, W, Cin,
                   Cout, OH, OW, S, P, taps, fw, D, 0, (int)fd, cur_stream());
   return {y, c10::nullopt};
+}
+
+// ---------------------------------------------------------------------------
+// Depthwise 3x3 (csrc/dwconv3x3.hip): groups == C, padding 1, stride 1 or 2
+// ---------------------------------------------------------------------------
+
+static int dw_vec(const at::Tensor& t) {
+  return t.scalar_type() == at::kBFloat16 ? 8 : 4;
+}
+
+// An activation or gradient as the kernels take it. Returns true when the
+// tensor is empty (nothing to launch).
+static bool dw_check_act(const char* op, const char* name,
+                         const at::Tensor& t) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.dim() == 4, op, ": ", name, " must be 4-D (N, C, H, W), got ",
+              t.dim(), "-D");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 ||
+                  t.scalar_type() == at::kFloat,
+              op, ": ", name, " must be bf16 or fp32, got ", t.scalar_type());
+  if (t.numel() == 0) return true;
+  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name,
+              " must be channels_last-contiguous");
+  const int V = dw_vec(t);
+  TORCH_CHECK(t.size(1) % V == 0, op, ": C=", t.size(1),
+              " must be a multiple of ", V, " for ", t.scalar_type());
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+              " must be 16-byte aligned");
+  TORCH_CHECK(t.numel() / V < (1L << 31), op, ": ", name, " has ", t.numel(),
+              " elements, more than the kernels index");
+  return false;
+}
+
+static void dw_check_weight(const char* op, const at::Tensor& w,
+                            const at::Tensor& act) {
+  TORCH_CHECK(w.device() == act.device(), op, ": weight must be on ",
+              act.device(), ", got ", w.device());
+  TORCH_CHECK(w.scalar_type() == at::kFloat && w.dim() == 4 &&
+                  w.size(0) == act.size(1) && w.size(1) == 1 &&
+                  w.size(2) == 3 && w.size(3) == 3 && w.is_contiguous(),
+              op, ": weight must be the contiguous fp32 [C,1,3,3] parameter "
+              "with C=", act.size(1), ", got ", w.scalar_type(), " ",
+              w.sizes());
+}
+
+static void dw_check_stride(const char* op, long stride) {
+  TORCH_CHECK(stride == 1 || stride == 2, op, ": stride must be 1 or 2, got ",
+              stride);
+}
+
+static long dw_out(long in, long stride) { return (in - 1) / stride + 1; }
+
+static at::Tensor dwconv3x3_fwd(at::Tensor x, at::Tensor w, long stride) {
+  const char* op = "dwconv3x3_fwd";
+  dw_check_stride(op, stride);
+  const bool empty = dw_check_act(op, "x", x);
+  dw_check_weight(op, w, x);
+  const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const long OH = H > 0 ? dw_out(H, stride) : 0;
+  const long OW = W > 0 ? dw_out(W, stride) : 0;
+  auto y = at::empty({N, C, OH, OW}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  if (empty) return y;
+  tfosr_dwconv3x3_fwd(x.data_ptr(), w.data_ptr<float>(), y.data_ptr(),
+                      x.scalar_type() == at::kBFloat16, N, C, H, W, OH, OW,
+                      stride, cur_stream());
+  return y;
+}
+
+static at::Tensor dwconv3x3_dgrad(at::Tensor dy, at::Tensor w, long stride,
+                                  long H, long W) {
+  const char* op = "dwconv3x3_dgrad";
+  dw_check_stride(op, stride);
+  const bool empty = dw_check_act(op, "dy", dy);
+  dw_check_weight(op, w, dy);
+  TORCH_CHECK(H >= 0 && W >= 0, op, ": H and W must not be negative");
+  const long N = dy.size(0), C = dy.size(1);
+  const long OH = H > 0 ? dw_out(H, stride) : 0;
+  const long OW = W > 0 ? dw_out(W, stride) : 0;
+  TORCH_CHECK(dy.size(2) == OH && dy.size(3) == OW, op, ": a ", H, "x", W,
+              " input with stride ", stride, " gives ", OH, "x", OW,
+              ", the gradient is ", dy.size(2), "x", dy.size(3));
+  auto dx = at::empty({N, C, H, W}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  if (empty || dx.numel() == 0) return dx;
+  TORCH_CHECK(dx.numel() / dw_vec(dy) < (1L << 31), op, ": dx has ",
+              dx.numel(), " elements, more than the kernels index");
+  tfosr_dwconv3x3_dgrad(dy.data_ptr(), w.data_ptr<float>(), dx.data_ptr(),
+                        dy.scalar_type() == at::kBFloat16, N, C, H, W, OH, OW,
+                        stride, cur_stream());
+  return dx;
+}
+
+static at::Tensor dwconv3x3_wrw(at::Tensor dy, at::Tensor x, long stride) {
+  const char* op = "dwconv3x3_wrw";
+  dw_check_stride(op, stride);
+  const bool dy_empty = dw_check_act(op, "dy", dy);
+  const bool x_empty = dw_check_act(op, "x", x);
+  TORCH_CHECK(x.device() == dy.device(), op, ": x must be on ", dy.device(),
+              ", got ", x.device());
+  TORCH_CHECK(x.scalar_type() == dy.scalar_type(), op,
+              ": dy and x must have one dtype, got ", dy.scalar_type(),
+              " and ", x.scalar_type());
+  const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const long OH = H > 0 ? dw_out(H, stride) : 0;
+  const long OW = W > 0 ? dw_out(W, stride) : 0;
+  TORCH_CHECK(dy.size(0) == N && dy.size(1) == C && dy.size(2) == OH &&
+                  dy.size(3) == OW,
+              op, ": x ", x.sizes(), " with stride ", stride,
+              " gives a gradient of [", N, ", ", C, ", ", OH, ", ", OW,
+              "], got ", dy.sizes());
+  auto opts = x.options().dtype(at::kFloat);
+  if (dy_empty || x_empty) return at::zeros({C, 1, 3, 3}, opts);
+  int grid_y, cvb, P, nblk;
+  long slab;
+  tfosr_dwconv3x3_wrw_plan(N * OH * OW, C / dw_vec(x), &grid_y, &cvb, &P,
+                           &nblk, &slab);
+  auto part = at::empty({(long)nblk, 9, C}, opts);
+  auto dw = at::empty({C, 1, 3, 3}, opts);
+  tfosr_dwconv3x3_wrw(dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(),
+                      dw.data_ptr<float>(), x.scalar_type() == at::kBFloat16,
+                      N, C, H, W, OH, OW, stride, cur_stream());
+  return dw;
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1426,6 +1557,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                       dx.data_ptr(), dy.scalar_type() == at::kBFloat16,
                       N, C, H, W, OH, OW, K, S, P, cur_stream());
     return dx;
+  });
+  m.def("dwconv3x3_fwd", &dwconv3x3_fwd, py::arg("x"), py::arg("w"),
+        py::arg("stride"));
+  m.def("dwconv3x3_dgrad", &dwconv3x3_dgrad, py::arg("dy"), py::arg("w"),
+        py::arg("stride"), py::arg("H"), py::arg("W"));
+  m.def("dwconv3x3_wrw", &dwconv3x3_wrw, py::arg("dy"), py::arg("x"),
+        py::arg("stride"));
+  // launch constants and the wrw split, for sizing tests and benchmarks
+  m.def("dwconv3x3_info", []() {
+    int block, max_grid, strip, pair, min_pix, max_blocks, fin_lanes;
+    tfosr_dwconv3x3_info(&block, &max_grid, &strip, &pair, &min_pix,
+                         &max_blocks, &fin_lanes);
+    py::dict d;
+    d["block"] = block;
+    d["max_grid"] = max_grid;
+    d["strip"] = strip;
+    d["pair"] = pair;
+    d["wrw_min_pix"] = min_pix;
+    d["wrw_max_blocks"] = max_blocks;
+    d["fin_lanes"] = fin_lanes;
+    return d;
+  });
+  m.def("dwconv3x3_wrw_plan", [](long M, long Cv) {
+    TORCH_CHECK(M > 0 && Cv > 0, "dwconv3x3_wrw_plan: M and Cv must be "
+                "positive");
+    int grid_y, cvb, P, nblk;
+    long slab;
+    tfosr_dwconv3x3_wrw_plan(M, (int)Cv, &grid_y, &cvb, &P, &nblk, &slab);
+    py::dict d;
+    d["grid_y"] = grid_y;
+    d["cvb"] = cvb;
+    d["P"] = P;
+    d["nblk"] = nblk;
+    d["slab"] = slab;
+    return d;
   });
 
   // native TFRecord codec (CPU): bulk scan/write with HW CRC32-C

@@ -15,7 +15,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.modules import ConvTranspose2dMFMA, DilatedConv3x3, FusedBNReLU
+from ..ops.modules import (ConvTranspose2dMFMA, DepthwiseConv3x3,
+                           DilatedConv3x3, FusedBNReLU)
 from .resnet import Bottleneck, ResNet, _maybe_pack_weights
 
 
@@ -26,6 +27,11 @@ class ConvBNReLU(nn.Sequential):
             # atrous 3x3: same parameters and init as the nn.Conv2d below,
             # routed to the in-tree MFMA kernels (TFOS_ATROUS)
             conv = DilatedConv3x3(cin, cout, dilation=dilation)
+        elif k == 3 and dilation == 1 and groups == cin == cout \
+                and stride in (1, 2):
+            # depthwise 3x3: same parameters and init as the nn.Conv2d
+            # below, routed to the in-tree streaming kernels (TFOS_DW)
+            conv = DepthwiseConv3x3(cin, stride=stride)
         else:
             conv = nn.Conv2d(cin, cout, k, stride, pad, groups=groups,
                              dilation=dilation, bias=False)

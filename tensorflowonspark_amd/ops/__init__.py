@@ -18,7 +18,7 @@ import torch
 logger = logging.getLogger(__name__)
 
 #: must match TFOSR_API_VERSION in csrc/bindings.cpp
-API_VERSION = 7
+API_VERSION = 8
 
 _ext = None
 _ext_checked = False

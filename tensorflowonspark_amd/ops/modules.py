@@ -870,6 +870,188 @@ class DilatedConv3x3(nn.Conv2d):
         return new
 
 
+# ---------------------------------------------------------------------------
+# Depthwise 3x3 convolution (csrc/dwconv3x3.hip)
+# ---------------------------------------------------------------------------
+
+_DW_DIRECTIONS = ("fwd", "dgrad", "wrw")
+
+
+def _dw_auto(direction, N, C, H, W, stride):
+    """TFOS_DW=auto policy: is ``direction`` ('fwd', 'dgrad' or 'wrw') of a
+    depthwise 3x3 conv over an N x C x H x W input routed to the in-tree
+    kernels?
+
+    Follows the isolated measurement of the 17 depthwise layers of
+    unet_mobilenet at b64 and b1024 @128^2 (tools/dw_bench.py,
+    docs/performance.md "Depthwise convolutions"), where a (shape,
+    direction) goes in-tree only if its median was no slower than the
+    library's in that run. _dw_table() is that table.
+
+    A shape that was not measured takes the decision of the measured shape
+    with the same stride whose input element count N*C*H*W is nearest (in
+    ratio), not the library: these are streaming kernels, and how they
+    stand against the library follows the tensor size. A stride that was
+    never measured (there is none among {1, 2}) stays on the library."""
+    rows = [r for r in _dw_table() if r[4] == stride]
+    if not rows:
+        return False
+    want = float(max(1, N * C * H * W))
+
+    def dist(r):
+        have = float(r[0] * r[1] * r[2] * r[3])
+        return max(have / want, want / have)
+
+    exact = [r for r in rows if r[:4] == (N, C, H, W)]
+    row = exact[0] if exact else min(rows, key=dist)
+    return row[5 + _DW_DIRECTIONS.index(direction)]
+
+
+def _dw_table():
+    """(N, C, H, W, stride, fwd, dgrad, wrw) per measured layer: True where
+    tools/dw_bench.py measured the in-tree kernel no slower than the library
+    on the MI355X (docs/performance.md "Depthwise convolutions"; the run is
+    profiles/unet_dw_bench.json, whose "auto" column this repeats)."""
+    T = True   # no pair lost: 2.4x to 18x (fwd, dgrad), 8x and up (wrw)
+    return (
+        (64, 32, 64, 64, 1, T, T, T),
+        (64, 96, 64, 64, 2, T, T, T),
+        (64, 144, 32, 32, 1, T, T, T),
+        (64, 144, 32, 32, 2, T, T, T),
+        (64, 192, 16, 16, 1, T, T, T),
+        (64, 192, 16, 16, 2, T, T, T),
+        (64, 384, 8, 8, 1, T, T, T),
+        (64, 576, 8, 8, 1, T, T, T),
+        (64, 576, 8, 8, 2, T, T, T),
+        (64, 960, 4, 4, 1, T, T, T),
+        (1024, 32, 64, 64, 1, T, T, T),
+        (1024, 96, 64, 64, 2, T, T, T),
+        (1024, 144, 32, 32, 1, T, T, T),
+        (1024, 144, 32, 32, 2, T, T, T),
+        (1024, 192, 16, 16, 1, T, T, T),
+        (1024, 192, 16, 16, 2, T, T, T),
+        (1024, 384, 8, 8, 1, T, T, T),
+        (1024, 576, 8, 8, 1, T, T, T),
+        (1024, 576, 8, 8, 2, T, T, T),
+        (1024, 960, 4, 4, 1, T, T, T),
+    )
+
+
+def _dw_route(N, C, H, W, stride):
+    """(fwd_in_tree, dgrad_in_tree, wrw_in_tree) for TFOS_DW, or None for
+    the plain library conv."""
+    mode = os.environ.get("TFOS_DW", "auto")
+    if mode == "miopen":
+        return None
+    if mode == "hip":
+        return True, True, True
+    if mode != "auto":
+        raise ValueError("TFOS_DW must be auto, hip or miopen, got "
+                         + repr(mode))
+    route = tuple(_dw_auto(d, N, C, H, W, stride) for d in _DW_DIRECTIONS)
+    return route if any(route) else None
+
+
+class _DepthwiseFn(torch.autograd.Function):
+    """Depthwise 3x3 conv (padding 1, stride 1 or 2) on channels_last bf16
+    or fp32 with the module's fp32 weight. Each of forward, dgrad and wrw
+    runs in-tree or through the library as its flag says; the library sees
+    the weight cast to the activation dtype, the value the kernels round to
+    on load."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride, fwd_in_tree, dgrad_in_tree,
+                wrw_in_tree):
+        if fwd_in_tree:
+            y = get_ext(required=True).dwconv3x3_fwd(x, weight, stride)
+        else:
+            y = F.conv2d(x, weight.to(x.dtype), None, stride, 1, 1,
+                         x.shape[1])
+        ctx.save_for_backward(x, weight)
+        ctx.stride = stride
+        ctx.in_tree = (dgrad_in_tree, wrw_in_tree)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        stride = ctx.stride
+        dgrad_in_tree, wrw_in_tree = ctx.in_tree
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        # an expanded (stride-0) gradient, as from y.sum().backward(),
+        # becomes a real channels_last tensor here
+        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if need_dx and dgrad_in_tree:
+            dx = get_ext(required=True).dwconv3x3_dgrad(
+                dy, weight, stride, x.shape[2], x.shape[3])
+        if need_dw and wrw_in_tree:
+            dw = get_ext(required=True).dwconv3x3_wrw(dy, x, stride)
+        lib_dx = need_dx and dx is None
+        lib_dw = need_dw and dw is None
+        if lib_dx or lib_dw:
+            gx, gw, _ = torch.ops.aten.convolution_backward(
+                dy, x, weight.to(x.dtype), None, [stride, stride], [1, 1],
+                [1, 1], False, [0, 0], x.shape[1], [lib_dx, lib_dw, False])
+            if lib_dx:
+                dx = gx
+            if lib_dw:
+                dw = gw.to(weight.dtype)
+        return dx, dw, None, None, None, None
+
+
+class DepthwiseConv3x3(nn.Conv2d):
+    """Depthwise 3x3 conv (groups == channels, padding 1, stride 1 or 2, no
+    bias) routed to the in-tree streaming kernels.
+
+    A subclass of nn.Conv2d so that parameter name, shape, the default
+    initialisation and the RNG draw order are exactly those of the
+    ``nn.Conv2d(C, C, 3, stride, 1, groups=C, bias=False)`` it stands in
+    for. Backend select via TFOS_DW: 'auto' (default: each of forward, dgrad
+    and wrw goes in-tree only where it was measured no slower than the
+    library, see _dw_auto), 'hip' (all three in-tree), 'miopen' (library
+    conv). CPU tensors, dtypes other than bf16/fp32 and channel counts that
+    are no multiple of the 16-byte vector (8 for bf16, 4 for fp32) stay on
+    the library path.
+    """
+
+    def __init__(self, channels, stride=1, device=None, dtype=None):
+        if int(stride) not in (1, 2):
+            raise ValueError("DepthwiseConv3x3 needs stride 1 or 2, got "
+                             + repr(stride))
+        super().__init__(channels, channels, 3, stride=int(stride), padding=1,
+                         groups=channels, bias=False, device=device,
+                         dtype=dtype)
+
+    def forward(self, x):
+        if x.is_cuda and x.dim() == 4 and self.weight.dtype == torch.float32:
+            # under autocast the library conv would run in the autocast
+            # dtype whatever x is; so does this path
+            dt = torch.get_autocast_dtype("cuda") \
+                if torch.is_autocast_enabled("cuda") else x.dtype
+            C = self.in_channels
+            vec = {torch.bfloat16: 8, torch.float32: 4}.get(dt)
+            if vec is not None and C % vec == 0 and x.numel() > 0:
+                route = _dw_route(x.shape[0], C, x.shape[2], x.shape[3],
+                                  self.stride[0])
+                if route is not None and get_ext(required=True) is not None:
+                    x = x.to(dt).contiguous(memory_format=torch.channels_last)
+                    return _DepthwiseFn.apply(x, self.weight, self.stride[0],
+                                              *route)
+        return super().forward(x)
+
+    def __prepare_scriptable__(self):
+        # the scripter must not compile the routed forward: hand it a plain
+        # grouped conv that shares the weight
+        _SCRIPT_CLONE_KEEPALIVE.append(self)
+        new = nn.Conv2d(self.in_channels, self.out_channels, 3,
+                        stride=self.stride, padding=1, groups=self.groups,
+                        bias=False)
+        new.weight = self.weight
+        new.train(self.training)
+        return new
+
+
 def _parity_launch(x, class_weight, out, k, pp, accum):
     """One conv_par launch per non-empty output parity class, each with only
     its valid taps; class_weight(ph, pw, rl, sl) is [OC, nr, ns, KC]."""
