@@ -80,6 +80,10 @@ void tfosr_conv3x3(const void*, const void*, const void*, void*, int, int, int,
 void tfosr_conv_mfma(const void*, const void*, const void*, void*, int, int,
                      int, int, int, int, int, int, int, int, int, int, int,
                      int, int, hipStream_t);
+int tfosr_conv3x3_halo_plan(int, int, int, int, int, int, int*, int*, long*,
+                            long*, int*);
+void tfosr_conv3x3_halo(const void*, const void*, void*, int, int, int, int,
+                        int, int, hipStream_t);
 void tfosr_conv_wrw(const void*, const void*, float*, int, int, int, int, int,
                     int, int, int, int, int, hipStream_t);
 int tfosr_wrw2_split(int, int, long);
@@ -1038,6 +1042,32 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // sum far inside the int range.
 static constexpr long kMaxTapReach = 1L << 20;
 
+// Which kernel a conv_mfma launch takes (csrc/conv3x3_halo.hip): the halo
+// kernel covers the plain 3x3 stride-1 padding-1 bf16 launch of natural
+// output size; TFOS_CONV3X3_TILE = auto | im2col | halo picks among the
+// eligible ones, anything else is an error.
+struct ConvTilePlan {
+  bool halo;
+  int bm, bn, max_w;
+  long tiles, grid;
+};
+
+static ConvTilePlan conv3x3_tile_plan(long N, long H, long W, long Cin,
+                                      long Cout, long fh, long fw, long S,
+                                      long P, long D, long OH, long OW,
+                                      long fd, bool out_f32, bool plain) {
+  const bool eligible = plain && fh == 3 && fw == 3 && S == 1 && P == 1 &&
+                        D == 1 && fd == 1 && !out_f32 && OH == H && OW == W;
+  ConvTilePlan p;
+  const int k = tfosr_conv3x3_halo_plan(eligible, (int)N, (int)H, (int)W,
+                                        (int)Cin, (int)Cout, &p.bm, &p.bn,
+                                        &p.tiles, &p.grid, &p.max_w);
+  TORCH_CHECK(k != -1, "TFOS_CONV3X3_TILE must be auto, im2col or halo");
+  TORCH_CHECK(k != -2, "TFOS_CONV3X3_HALO_BM must be 256 or 512");
+  p.halo = k == 1;
+  return p;
+}
+
 // conv_mfma and conv_mfma_stats (see their m.def below). stats: also return
 // the output's BatchNorm tile partials [ceil(N*OH*OW / 256)][2][Cout] where
 // the launch has the statistics epilogue (input dilation 1, bf16 output).
@@ -1079,6 +1109,10 @@ static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
                      x.options().dtype(out_f32 ? at::kFloat : at::kBFloat16),
                      at::MemoryFormat::ChannelsLast);
   const void* guard = zero_guard(x);
+  // before either launch, so that a bad TFOS_CONV3X3_TILE is an error on
+  // every path; a launch with the statistics epilogue is never eligible
+  const ConvTilePlan plan = conv3x3_tile_plan(N, H, W, Cin, Cout, fh, fw, S, P,
+                                              D, OH, OW, fd, out_f32, !stats);
   if (stats && D == 1 && !out_f32) {
     TORCH_CHECK(x.is_cuda() && wk.device() == x.device(),
                 "conv_mfma_stats: x and wk must be on one GPU");
@@ -1090,6 +1124,13 @@ static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
                           part.data_ptr<float>(), N, H, W, Cin, Cout, OH, OW, S,
                           P, taps, fw, (int)fd, cur_stream());
     return {y, part};
+  }
+  if (plan.halo) {
+    TORCH_CHECK(x.is_cuda() && wk.device() == x.device(),
+                "conv_mfma: x and wk must be on one GPU");
+    tfosr_conv3x3_halo(x.data_ptr(), wk.contiguous().data_ptr(), y.data_ptr(),
+                       plan.bm, N, H, W, Cin, (int)Cout, cur_stream());
+    return {y, c10::nullopt};
   }
   tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard,
                   y.data_ptr(), /*out_bf16=*/out_f32 ? 0 : 1, N, H, W, Cin,
@@ -1309,6 +1350,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("x"), py::arg("wk"), py::arg("Cout"), py::arg("fh"),
      py::arg("fw"), py::arg("S"), py::arg("P"), py::arg("D"), py::arg("OH"),
      py::arg("OW"), py::arg("fd") = 1, py::arg("out_f32") = false);
+  // Host only: the kernel conv_mfma would launch for this call under the
+  // current TFOS_CONV3X3_TILE, with its tile, tile count and grid, and the
+  // largest W the halo kernel can stage (OH/OW < 0: the natural size).
+  m.def("conv3x3_halo_plan", [](long N, long H, long W, long Cin, long Cout,
+                                long fh, long fw, long S, long P, long D,
+                                long OH, long OW, long fd, bool out_f32) {
+    TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && S > 0 &&
+                fd > 0 && D > 0, "conv3x3_halo_plan: bad dims");
+    if (OH < 0) {
+      OH = ((H - 1) * D + 1 + 2 * P - fd * (fh - 1) - 1) / S + 1;
+      OW = ((W - 1) * D + 1 + 2 * P - fd * (fw - 1) - 1) / S + 1;
+    }
+    const ConvTilePlan p = conv3x3_tile_plan(N, H, W, Cin, Cout, fh, fw, S, P,
+                                             D, OH, OW, fd, out_f32, true);
+    py::dict d;
+    d["kernel"] = p.halo ? "halo" : "im2col";
+    d["BM"] = p.bm;
+    d["BN"] = p.bn;
+    d["tiles"] = p.tiles;
+    d["grid"] = p.grid;
+    d["max_w"] = p.max_w;
+    return d;
+  }, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"),
+     py::arg("Cout"), py::arg("fh") = 3, py::arg("fw") = 3, py::arg("S") = 1,
+     py::arg("P") = 1, py::arg("D") = 1, py::arg("OH") = -1,
+     py::arg("OW") = -1, py::arg("fd") = 1, py::arg("out_f32") = false);
   // -> (y, part, rows_per_tile): y is conv_mfma(...) bit for bit; part holds
   // y's per-tile BatchNorm partials for bn_fwd_train_pre, or None
   // (rows_per_tile 0) where the launch has no statistics epilogue (input

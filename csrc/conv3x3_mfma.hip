@@ -11,6 +11,10 @@
 //
 // Same 4-deep LDS ring + counted-vmcnt pipeline as gemm_bt256 (no vmcnt(0)
 // in the main loop); two tile shapes: 256x256 (Cout >= 192) and 256x128.
+// The plain 3x3 stride-1 padding-1 bf16 launch has a second kernel that
+// walks K chunk-major and stages every input chunk once with its halo
+// (conv3x3_halo.hip); the binding chooses between the two per launch
+// (TFOS_CONV3X3_TILE), everything else stays here.
 // Backward-data for stride 1 reuses this kernel: dx = conv3x3(dy, W') with
 // W'[cin][r][s][cout] = W[cout][2-r][2-s][cin] (built host-side).
 //

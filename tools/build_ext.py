@@ -20,7 +20,7 @@ OUT_SO = os.path.join(OUT_DIR, "tfosr_hip_ops.so")
 BUILD = os.path.join(REPO, "build", "hip")
 
 SOURCES = ["bn_relu.hip", "softmax_xent_dense.hip", "elementwise.hip",
-           "gemm_mfma.hip", "conv3x3_mfma.hip", "conv_wrw_mfma.hip", "conv_wrw2.hip", "maxpool.hip", "dwconv3x3.hip",
+           "gemm_mfma.hip", "conv3x3_mfma.hip", "conv3x3_halo.hip", "conv_wrw_mfma.hip", "conv_wrw2.hip", "maxpool.hip", "dwconv3x3.hip",
            "tfrecord_codec.cpp", "bindings.cpp"]
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

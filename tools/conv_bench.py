@@ -6,6 +6,7 @@ Covers the ResNet-50 stride-2 shapes and the U-Net decoder transposed convs
     python tools/conv_bench.py [--batch 1024]
     python tools/conv_bench.py --atrous [--batch 32] [--rounds 9]
     python tools/conv_bench.py --wrwtail --parent-ext OLD/tfosr_hip_ops_parent.so
+    python tools/conv_bench.py --halo [--parent-ext OLD/tfosr_hip_ops_parent.so]
 """
 
 import argparse
@@ -62,6 +63,11 @@ def main():
     ap.add_argument("--wrwtail", action="store_true",
                     help="split-M reduce and stem wrw: this tree's extension "
                          "against another build of it (--parent-ext)")
+    ap.add_argument("--halo", action="store_true",
+                    help="3x3 stride-1 shapes: TFOS_CONV3X3_TILE=im2col "
+                         "against halo (both tile heights), alternating")
+    ap.add_argument("--halo-shapes", default=None,
+                    help="comma-separated tags to restrict --halo to")
     ap.add_argument("--parent-ext", default=None,
                     help="extension of the commit to compare against, built under "
                          "a module name of its own (see load_ext_from)")
@@ -76,6 +82,10 @@ def main():
     if args.wrwtail:
         bench_wrwtail(args.batch, args.parent_ext, max(args.rounds, 7),
                       args.iters, args.json)
+        return
+    if args.halo:
+        bench_halo(args.batch, args.parent_ext, args.rounds, args.iters,
+                   args.json, args.halo_shapes)
         return
     if args.atrous:
         bench_atrous(32 if args.batch == 1024 else args.batch, args.rounds,
@@ -350,6 +360,92 @@ def bench_wrwtail(batch=1024, parent_ext=None, rounds=7, iters=5,
               flush=True)
         rows.append(dict(tag=tag, batch=N, split=split, n=n, ws_mb=mb,
                          ms=med, spread=spread))
+    if json_path:
+        os.makedirs(os.path.dirname(os.path.abspath(json_path)),
+                    exist_ok=True)
+        with open(json_path, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+def bench_halo(batch=1024, parent_ext=None, rounds=9, iters=5,
+               json_path=None, only=None):
+    """conv_mfma on the plain 3x3 stride-1 launch, forward (w9 pack) and
+    dgrad (flipped pack; the same launch on dy): the im2col kernel against
+    the halo kernel at both tile heights, switched per call through
+    TFOS_CONV3X3_TILE / TFOS_CONV3X3_HALO_BM (read at call time), alternating
+    in one process; --parent-ext adds the parent's build. `auto` is timed as
+    well, so the table shows what the default routing launches."""
+    import json
+    from tensorflowonspark_amd.ops import get_ext
+    ext = get_ext(required=True)
+    parent = load_ext_from(parent_ext) if parent_ext else None
+    bf16 = torch.bfloat16
+    torch.manual_seed(0)
+    # tag, N, C, H=W
+    shapes = [
+        ("64@56", batch, 64, 56), ("128@28", batch, 128, 28),
+        ("256@14", batch, 256, 14), ("512@7", batch, 512, 7),
+        # segmentation-sized launches (no model in the tree routes them here
+        # yet): a U-Net decoder level and a DeepLab head, at their batches
+        ("unet 64@128 b64", max(1, batch // 16), 64, 128),
+        ("deeplab 256@33 b32", max(1, batch // 32), 256, 33),
+        # small M, to place the `auto` threshold
+        ("64@56 b64", max(1, batch // 16), 64, 56),
+        ("64@56 b8", max(1, batch // 128), 64, 56),
+        ("128@28 b32", max(1, batch // 32), 128, 28),
+    ]
+    if only:
+        keep = set(only.split(","))
+        shapes = [s for s in shapes if s[0] in keep]
+
+    def side(e, mode, bm, x, w, C):
+        def run():
+            os.environ["TFOS_CONV3X3_TILE"] = mode
+            if bm:
+                os.environ["TFOS_CONV3X3_HALO_BM"] = str(bm)
+            else:
+                os.environ.pop("TFOS_CONV3X3_HALO_BM", None)
+            return e.conv_mfma(x, w, C, 3, 3, 1, 1, 1, -1, -1)
+        return run
+
+    rows = []
+    for tag, N, C, hw in shapes:
+        x = (torch.randn(N, C, hw, hw, device="cuda") / 4).to(bf16) \
+            .contiguous(memory_format=torch.channels_last)
+        w4 = (torch.randn(C, C, 3, 3, device="cuda") / 16).to(bf16)
+        packs = {"fwd": w4.permute(0, 2, 3, 1).reshape(C, -1).contiguous(),
+                 "dgrad": w4.flip(2, 3).permute(1, 2, 3, 0).reshape(C, -1)
+                 .contiguous()}
+        for what, w in packs.items():
+            sides = {"im2col": side(ext, "im2col", 0, x, w, C),
+                     "halo512": side(ext, "halo", 512, x, w, C),
+                     "halo256": side(ext, "halo", 256, x, w, C),
+                     "auto": side(ext, "auto", 0, x, w, C)}
+            if parent is not None:
+                sides["parent"] = side(parent, "auto", 0, x, w, C)
+            plans = {}
+            for k, fn in sides.items():
+                y = fn()
+                if k != "parent":
+                    pl = ext.conv3x3_halo_plan(N, hw, hw, C, C)
+                    plans[k] = "{}{}".format(pl["kernel"], pl["BM"])
+                if k == "im2col":
+                    base = y.double()
+                else:
+                    d = (y.double() - base).abs().max().item()
+                    assert d <= 2.0 ** -7 * base.abs().max().item(), (tag, k)
+            spread = {}
+            med = ab_median(sides, rounds, iters, spread)
+            gflop = 2.0 * N * hw * hw * C * C * 9 / 1e9
+            cells = "  ".join("{} {:.4f} ms ({:.0f} TF/s, spread {:.4f})"
+                              .format(k, v, gflop / v, spread[k])
+                              for k, v in med.items())
+            print("{} {} N={}: {} | plans {}".format(tag, what, N, cells,
+                                                    plans), flush=True)
+            rows.append(dict(tag=tag, what=what, N=N, C=C, hw=hw, ms=med,
+                             spread=spread, plans=plans, gflop=gflop))
+    os.environ.pop("TFOS_CONV3X3_TILE", None)
+    os.environ.pop("TFOS_CONV3X3_HALO_BM", None)
     if json_path:
         os.makedirs(os.path.dirname(os.path.abspath(json_path)),
                     exist_ok=True)
