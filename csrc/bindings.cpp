@@ -11,6 +11,8 @@
 
 extern "C" {
 int tfosr_bn_fast_blocks(long, int, int, int);
+int tfosr_bn_rows_mode();
+int tfosr_bn_rows_plan(long, int, int, int, int*, int*);
 void tfosr_bn_apply_dual(const void*, const void*, void*, unsigned char*,
                          const float*, const float*, const float*, const float*,
                          const float*, const float*, const float*, const float*,
@@ -216,6 +218,32 @@ void bn_check_like(const at::Tensor& t, const at::Tensor& x, bool nhwc,
   }
 }
 
+// Which tier of csrc/bn_relu.hip a tensor takes and the rows of partials its
+// reductions write: the NHWC fast path, the NHWC row tier (TFOS_BN_ROWS = on,
+// the default, or off; read at every call, anything else is an error) or,
+// with nb == 0, the generic kernels, which add into a ZEROED [2C] workspace.
+// Only the fast path writes and reads the ReLU bitmask.
+struct BNTier {
+  int nb;
+  bool fast;
+  int pixel_lanes, threads;  // of the row tier, else 0
+};
+
+static BNTier bn_tier(long total, int C, int bf, int nhwc) {
+  TORCH_CHECK(tfosr_bn_rows_mode() >= 0, "TFOS_BN_ROWS must be on or off");
+  BNTier t = {tfosr_bn_fast_blocks(total, C, bf, nhwc), true, 0, 0};
+  if (t.nb > 0) return t;
+  t.fast = false;
+  t.nb = tfosr_bn_rows_plan(total, C, bf, nhwc, &t.pixel_lanes, &t.threads);
+  return t;
+}
+
+static at::Tensor bn_workspace(const BNTier& t, int C,
+                               const at::TensorOptions& opts) {
+  return t.nb > 0 ? at::empty({(long)t.nb * 2 * C}, opts)
+                  : at::zeros({2L * C}, opts);
+}
+
 std::vector<at::Tensor> bn_fwd_train(at::Tensor x, c10::optional<at::Tensor> res,
                                      at::Tensor w, at::Tensor b, at::Tensor rm,
                                      at::Tensor rv, double momentum, double eps,
@@ -233,16 +261,16 @@ std::vector<at::Tensor> bn_fwd_train(at::Tensor x, c10::optional<at::Tensor> res
   bn_check_channel_vec(rv, x, l.C, "running_var");
   auto opts = x.options().dtype(at::kFloat);
   long M = (long)l.N * l.HW;
-  int nb = tfosr_bn_fast_blocks(M * l.C, l.C, bf, l.nhwc);
-  auto ws = nb > 0 ? at::empty({(long)nb * 2 * l.C}, opts)
-                   : at::zeros({2L * l.C}, opts);
+  const BNTier tier = bn_tier(M * l.C, l.C, bf, l.nhwc);
+  const int nb = tier.nb;
+  auto ws = bn_workspace(tier, l.C, opts);
   auto save_mean = at::empty({l.C}, opts);
   auto save_rstd = at::empty({l.C}, opts);
   auto y = at::empty_like(x);
   // relu sign bitmask (1 byte per vector) for y-free backward gating
   at::Tensor mask;
   unsigned char* mask_ptr = nullptr;
-  if (relu && nb > 0) {
+  if (relu && tier.fast) {
     long nvec = M * l.C / (bf ? 8 : 4);
     mask = at::empty({nvec}, x.options().dtype(at::kByte));
     mask_ptr = mask.data_ptr<unsigned char>();
@@ -277,6 +305,7 @@ at::Tensor bn_fwd_eval(at::Tensor x, c10::optional<at::Tensor> res, at::Tensor w
   bn_check_channel_vec(b, x, l.C, "bias");
   bn_check_channel_vec(rm, x, l.C, "running_mean");
   bn_check_channel_vec(rv, x, l.C, "running_var");
+  TORCH_CHECK(tfosr_bn_rows_mode() >= 0, "TFOS_BN_ROWS must be on or off");
   auto rstd = at::rsqrt(rv + eps);
   auto y = at::empty_like(x);
   tfosr_bn_apply(x.data_ptr(), res_ptr, y.data_ptr(), nullptr,
@@ -301,9 +330,9 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y,
   dy = l.nhwc ? dy.contiguous(at::MemoryFormat::ChannelsLast) : dy.contiguous();
   auto opts = x.options().dtype(at::kFloat);
   long total = (long)l.N * l.HW * l.C;
-  int nb = tfosr_bn_fast_blocks(total, l.C, bf, l.nhwc);
-  auto ws = nb > 0 ? at::empty({(long)nb * 2 * l.C}, opts)
-                   : at::zeros({2L * l.C}, opts);
+  const BNTier tier = bn_tier(total, l.C, bf, l.nhwc);
+  const int nb = tier.nb;
+  auto ws = bn_workspace(tier, l.C, opts);
   auto dg = at::empty({l.C}, opts);
   auto db = at::empty({l.C}, opts);
   auto dx = at::empty_like(x);
@@ -316,9 +345,9 @@ std::vector<at::Tensor> bn_bwd(at::Tensor x, at::Tensor dy, at::Tensor y,
   auto s = cur_stream();
   const unsigned char* mask_ptr =
       mask.numel() ? mask.data_ptr<unsigned char>() : nullptr;
-  TORCH_CHECK(!(relu && nb > 0) || mask_ptr != nullptr,
+  TORCH_CHECK(!(relu && tier.fast) || mask_ptr != nullptr,
               "fast-path relu backward requires the forward bitmask");
-  if (relu && nb > 0) {
+  if (relu && tier.fast) {
     TORCH_CHECK(mask.device() == x.device() && mask.scalar_type() == at::kByte &&
                     mask.is_contiguous() && mask.numel() == total / (bf ? 8 : 4),
                 "bn: mask must be the contiguous uint8 bitmask bn_fwd_train "
@@ -614,30 +643,37 @@ std::vector<at::Tensor> bn_dual_bwd(at::Tensor xa, at::Tensor xb, at::Tensor dy,
   return {dxa, dxb, dg_a, dg_b, db_a, db_b};
 }
 
-// One launch of one NHWC fast-path kernel family on caller-owned tensors, so
+// One launch of one BatchNorm kernel family on caller-owned tensors, in the
+// tier bn_fwd_train / bn_bwd would take for x (fast path, row tier, generic), so
 // that tools/bn_bench.py can time stats, apply, bwd stats and bwd dx apart
 // (bn_fwd_train / bn_bwd run three launches each). family: 0 stats (x -> ws),
 // 1 apply (x, other = res or none -> out, mask), 2 bwd stats (x, other = dy,
 // mask -> ws, out = gout or none), 3 bwd dx (x, other = dy, mask -> out).
 // p0..p3 are per-channel fp32 vectors: mean, rstd, weight, bias for apply;
 // mean, rstd for bwd stats; mean, rstd, weight, dgamma for bwd dx with
-// dbeta in p4. ws holds bn_fast_blocks() * 2C floats.
+// dbeta in p4. ws holds max(nb, 1) * 2C floats, nb = bn_fast_blocks() or else
+// bn_rows_plan()[0]; the generic kernels (nb == 0) add into it, so the sums
+// mean something only if the caller zeroed it. Off the fast path the mask is
+// not used and a ReLU backward gates on y, which it then needs.
 void bn_stage(int family, at::Tensor x, c10::optional<at::Tensor> other,
               c10::optional<at::Tensor> out, c10::optional<at::Tensor> mask,
-              at::Tensor ws, std::vector<at::Tensor> p, bool relu) {
+              at::Tensor ws, std::vector<at::Tensor> p, bool relu,
+              c10::optional<at::Tensor> y) {
   auto l = bn_layout(x);
   int bf = dtype_flag(x);
   long total = (long)l.N * l.HW * l.C;
-  int nb = tfosr_bn_fast_blocks(total, l.C, bf, l.nhwc);
-  TORCH_CHECK(nb > 0, "bn_stage: shape is not on the NHWC fast path");
+  const BNTier tier = bn_tier(total, l.C, bf, l.nhwc);
+  const int nb = tier.nb;
+  TORCH_CHECK(l.nhwc, "bn_stage: expects a channels_last tensor");
   const size_t need[4] = {0, 4, 2, 5};
   TORCH_CHECK(family >= 0 && family < 4, "bn_stage: family must be 0..3");
   TORCH_CHECK(p.size() == need[family], "bn_stage: family ", family, " takes ",
               need[family], " per-channel vectors");
   for (auto& t : p) bn_check_channel_vec(t, x, l.C, "per-channel vector");
   TORCH_CHECK(ws.device() == x.device() && ws.scalar_type() == at::kFloat &&
-                  ws.is_contiguous() && ws.numel() >= (long)nb * 2 * l.C,
-              "bn_stage: ws must hold bn_fast_blocks() * 2C floats");
+                  ws.is_contiguous() &&
+                  ws.numel() >= (long)(nb > 0 ? nb : 1) * 2 * l.C,
+              "bn_stage: ws must hold max(nb, 1) * 2C floats");
   const void* other_ptr = nullptr;
   if (other.has_value()) {
     bn_check_like(*other, x, l.nhwc, true, "other");
@@ -660,8 +696,14 @@ void bn_stage(int family, at::Tensor x, c10::optional<at::Tensor> other,
     TORCH_CHECK(other_ptr != nullptr, "bn_stage: dy is required");
   if (family == 1 || family == 3)
     TORCH_CHECK(out_ptr != nullptr, "bn_stage: out is required");
+  const void* y_ptr = nullptr;
+  if (y.has_value()) {
+    bn_check_like(*y, x, l.nhwc, true, "y");
+    y_ptr = y->data_ptr();
+  }
   if (family >= 2)
-    TORCH_CHECK(!relu || mask_ptr != nullptr, "bn_stage: relu needs the mask");
+    TORCH_CHECK(!relu || (tier.fast ? (const void*)mask_ptr : y_ptr) != nullptr,
+                "bn_stage: relu needs the mask on the fast path, y elsewhere");
   auto f = [&](size_t i) { return p[i].data_ptr<float>(); };
   auto s = cur_stream();
   switch (family) {
@@ -674,12 +716,12 @@ void bn_stage(int family, at::Tensor x, c10::optional<at::Tensor> other,
                      f(2), f(3), bf, 1, relu, total, l.C, l.HW, s);
       break;
     case 2:
-      tfosr_bn_bwd_stats(x.data_ptr(), other_ptr, nullptr, mask_ptr, out_ptr,
+      tfosr_bn_bwd_stats(x.data_ptr(), other_ptr, y_ptr, mask_ptr, out_ptr,
                          f(0), f(1), ws.data_ptr<float>(), nb, bf, 1, relu,
                          l.N, l.C, l.HW, s);
       break;
     default:
-      tfosr_bn_bwd_dx(x.data_ptr(), other_ptr, nullptr, mask_ptr, f(0), f(1),
+      tfosr_bn_bwd_dx(x.data_ptr(), other_ptr, y_ptr, mask_ptr, f(0), f(1),
                       f(2), f(3), f(4), out_ptr, bf, 1, relu, total, l.C, l.HW,
                       s);
   }
@@ -1274,7 +1316,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_fast_blocks", [](long total, int C, bool bf16, bool nhwc) {
     return tfosr_bn_fast_blocks(total, C, bf16, nhwc);
   });
-  m.def("bn_stage", &bn_stage);
+  // the row tier's launch shape for a tensor of `total` elements: (reduction
+  // blocks, pixel lanes, threads per block); blocks == 0: not the row tier
+  m.def("bn_rows_plan", [](long total, int C, bool bf16, bool nhwc) {
+    const BNTier t = bn_tier(total, C, bf16, nhwc);
+    return t.fast ? std::make_tuple(0, 0, 0)
+                  : std::make_tuple(t.nb, t.pixel_lanes, t.threads);
+  });
+  m.def("bn_stage", &bn_stage, py::arg("family"), py::arg("x"),
+        py::arg("other"), py::arg("out"), py::arg("mask"), py::arg("ws"),
+        py::arg("p"), py::arg("relu"), py::arg("y") = py::none());
   m.def("softmax_xent_fwd", &softmax_xent_fwd);
   m.def("softmax_xent_bwd", &softmax_xent_bwd);
   m.def("xent_dense_fwd", &xent_dense_fwd, py::arg("logits"), py::arg("target"),

@@ -1,6 +1,8 @@
 // Fused BatchNorm2d (+residual add)(+ReLU) for gfx950 — training fwd/bwd and
-// eval fwd, NHWC (channels_last) fast path + generic fallbacks, fp32/bf16
-// activations with fp32 statistics.
+// eval fwd, fp32/bf16 activations with fp32 statistics. Three dispatch tiers:
+// the NHWC (channels_last) fast path for C | 2048, the NHWC row tier for the
+// other widths that are a multiple of the vector (see its section), and the
+// generic fallbacks for everything else.
 //
 // These ops are HBM-bound on MI355X; the design rules applied here:
 //  * 16 B/lane vector access everywhere (8 bf16 / 4 f32 per thread) — hipcc
@@ -11,17 +13,21 @@
 //  * NHWC reductions: a thread owns the fixed channels of its first vector,
 //    (i*V .. i*V+V-1) mod C, accumulating in registers over a grid-stride
 //    loop, one LDS atomicAdd per channel at the end. Valid when C | 2048
-//    (every ResNet/UNet width) and the grid stride is a multiple of C, which
-//    grid_quantum() guarantees.
+//    (every ResNet width and the U-Net decoder's; the MobileNetV2 encoder's
+//    24 .. 960 go to the row tier) and the grid stride is a multiple of C,
+//    which grid_quantum() guarantees.
 //  * statistics are accumulated around a per-channel shift (the first pixel's
-//    value on the fast path, the mean of the first 32 pixels on the generic
-//    one), so the single-pass E[d^2]-E[d]^2 variance does not cancel when
+//    value on the fast path, the mean of the first 32 pixels on the row and
+//    generic ones), so the single-pass E[d^2]-E[d]^2 variance does not cancel when
 //    |mean| >> std.
 //  * fusion: the residual add and ReLU fold into the normalize pass (fwd) and
 //    the dgamma/dbeta pass emits the gated upstream gradient (bwd) so the
 //    elementwise add/relu/relu' kernels and their whole-tensor round trips
 //    disappear.
 #include "tfosr_common.h"
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 typedef unsigned int u32;
 
@@ -36,7 +42,7 @@ template <>
 struct VecIO<bf16_t> {
   static constexpr int V = 8;
   using vec_t = s8v;
-  __device__ static void load(const bf16_t* p, float* out) {
+  __device__ __forceinline__ static void load(const bf16_t* p, float* out) {
     vec_t v = *(const vec_t*)p;
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -45,7 +51,7 @@ struct VecIO<bf16_t> {
       out[j] = (float)u.b;
     }
   }
-  __device__ static void store(bf16_t* p, const float* in) {
+  __device__ __forceinline__ static void store(bf16_t* p, const float* in) {
     vec_t v;
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -61,12 +67,12 @@ template <>
 struct VecIO<float> {
   static constexpr int V = 4;
   using vec_t = f4v;
-  __device__ static void load(const float* p, float* out) {
+  __device__ __forceinline__ static void load(const float* p, float* out) {
     f4v v = *(const f4v*)p;
     #pragma unroll
     for (int j = 0; j < 4; ++j) out[j] = v[j];
   }
-  __device__ static void store(float* p, const float* in) {
+  __device__ __forceinline__ static void store(float* p, const float* in) {
     f4v v;
     #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = in[j];
@@ -604,6 +610,279 @@ __global__ void bwd_dx_dual_fast(const T* __restrict__ xa,
 }
 
 // ---------------------------------------------------------------------------
+// NHWC row tier — C % V == 0, C / V <= 256 and total < 2^31, for the widths
+// the fast path does not take (C does not divide 2048: 24, 96, 144, 160, 192,
+// 320, 384, 576, 960 in the MobileNetV2 encoder).
+//
+// With Cv = C / V channel vectors per pixel, a block's threads form P pixel
+// lanes x Cv channel-vector lanes (P = threads / Cv, the remainder idles).
+// Thread (p, cv) owns channels cv*V .. cv*V+V-1 for its whole life and walks
+// pixels p, p+P, ... of its range, so one iteration of a block reads P*C
+// contiguous elements as 16 B vectors and the loops hold no division: the only
+// one is the split of threadIdx.x below. Reductions add up in registers, then
+// combine the P pixel lanes by a fixed tree through LDS [P][2C] (<= 16 KB) and
+// write partials[block][2C] for stats_merge_finalize / bwd_stats_merge: no
+// atomics anywhere, so results repeat bit for bit. There is no ReLU bitmask in
+// this tier: backward gates on y > 0 as the generic kernels do.
+// ---------------------------------------------------------------------------
+
+// The row kernels are compiled without packed fp32 VALU instructions (the
+// attribute reaches what is inlined into them; the device pass only, the host
+// stubs have no such feature). The rest of the file is built as before.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TFOSR_ROWS_KERNEL __global__ __attribute__((target("no-packed-fp32-ops")))
+#else
+#define TFOSR_ROWS_KERNEL __global__
+#endif
+
+struct RowLane {
+  u32 p, c0;  // pixel lane, first channel
+  bool on;    // false for the threads past P * Cv
+};
+
+template <int V>
+__device__ __forceinline__ RowLane row_lane(u32 Cv, u32 P) {
+  RowLane l;
+  l.p = threadIdx.x / Cv;
+  l.c0 = (threadIdx.x - l.p * Cv) * (u32)V;
+  l.on = l.p < P;
+  return l;
+}
+
+// per-channel parameters: plain loads, a caller's vector need not be 16 B aligned
+template <int V>
+__device__ __forceinline__ void chan_get(const float* __restrict__ p, float* out) {
+  #pragma unroll
+  for (int j = 0; j < V; ++j) out[j] = p[j];
+}
+
+// 16 B moves of the thread's V floats to and from LDS and the partials
+template <int V>
+__device__ __forceinline__ void vec_get(const float* __restrict__ p, float* out) {
+  #pragma unroll
+  for (int i = 0; i < V; i += 4) {
+    f4v t = *(const f4v*)(p + i);
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) out[i + j] = t[j];
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void vec_put(float* __restrict__ p, const float* in) {
+  #pragma unroll
+  for (int i = 0; i < V; i += 4) {
+    f4v t;
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = in[i + j];
+    *(f4v*)(p + i) = t;
+  }
+}
+
+// Sum a[] and b[] over the P pixel lanes of every channel vector through
+// lds[P][2C], pairing row p with row p + s for s = P2/2, P2/4, ..., 1 (P2 the
+// power of two >= P): depth log2(P), the same order in every run. The totals
+// end in the registers of pixel lane 0. Every thread of the block calls it.
+template <int V>
+__device__ __forceinline__ void rows_reduce(float (&a)[V], float (&b)[V],
+                                            float* lds, const RowLane& l,
+                                            u32 C, u32 P) {
+  float* row = lds + l.p * 2 * C + l.c0;  // dereferenced by live lanes only
+  if (l.on && P > 1) {
+    vec_put<V>(row, a);
+    vec_put<V>(row + C, b);
+  }
+  u32 p2 = 1;
+  while (p2 < P) p2 <<= 1;
+  u32 n = P;  // rows still holding a partial sum
+  for (u32 s = p2 >> 1; s > 0; s >>= 1) {
+    __syncthreads();
+    if (l.on && l.p < s && l.p + s < n) {
+      float oa[V], ob[V];
+      vec_get<V>(row + s * 2 * C, oa);
+      vec_get<V>(row + s * 2 * C + C, ob);
+      #pragma unroll
+      for (int j = 0; j < V; ++j) { a[j] += oa[j]; b[j] += ob[j]; }
+      if (s > 1) {
+        vec_put<V>(row, a);
+        vec_put<V>(row + C, b);
+      }
+    }
+    if (n > s) n = s;
+  }
+}
+
+// Stage A of the statistics: block b takes pixels [b*ppb, (b+1)*ppb), ppb a
+// multiple of P. The shift is the generic tier's, channel_shift(..., nshift):
+// pixel lane 0 adds its channels' first nshift pixels in index order and
+// hands the result to the other lanes through LDS.
+template <typename T>
+TFOSR_ROWS_KERNEL void stats_rows(const T* __restrict__ x, float* __restrict__ partials,
+                           u32 M, u32 C, u32 Cv, u32 P, u32 ppb, u32 nshift) {
+  extern __shared__ float lds[];  // [P][2C]
+  constexpr int V = VecIO<T>::V;
+  const RowLane l = row_lane<V>(Cv, P);
+  float k[V], s[V], q[V], v[V];
+  #pragma unroll
+  for (int j = 0; j < V; ++j) { k[j] = 0.f; s[j] = 0.f; q[j] = 0.f; }
+  if (l.on && l.p == 0) {
+    u32 off = l.c0;
+    // unrolled so that the loads go out together: as a plain loop the kernel
+    // took 8.0 us on 64x160x4x4 against the generic kernel's 6.4, now 5.4
+    #pragma unroll 8
+    for (u32 m = 0; m < nshift; ++m, off += C) {
+      VecIO<T>::load(x + off, v);
+      #pragma unroll
+      for (int j = 0; j < V; ++j) k[j] += v[j];
+    }
+    #pragma unroll
+    for (int j = 0; j < V; ++j) k[j] = k[j] / (float)nshift;
+    vec_put<V>(lds + l.c0, k);
+  }
+  __syncthreads();
+  if (l.on) vec_get<V>(lds + l.c0, k);
+  __syncthreads();  // the reduce below writes over the shifts
+  const u32 m0 = blockIdx.x * ppb;
+  const u32 m1 = m0 + ppb < M ? m0 + ppb : M;
+  if (l.on) {
+    const u32 end = m1 * C, step = P * C;
+    #pragma unroll 4
+    for (u32 off = (m0 + l.p) * C + l.c0; off < end; off += step) {
+      VecIO<T>::load(x + off, v);
+      #pragma unroll
+      for (int j = 0; j < V; ++j) { float d = v[j] - k[j]; s[j] += d; q[j] += d * d; }
+    }
+  }
+  rows_reduce<V>(s, q, lds, l, C, P);
+  if (l.on && l.p == 0) {
+    float* out = partials + (size_t)blockIdx.x * 2 * C + l.c0;
+    vec_put<V>(out, s);
+    vec_put<V>(out + C, q);
+  }
+}
+
+// normalize (+add residual)(+relu): block b takes the pixel groups b,
+// b + gridDim.x, ... of P pixels each; mean, rstd, weight and bias of the
+// thread's channels sit in registers for the whole stream
+template <typename T, bool RELU, bool ADD>
+TFOSR_ROWS_KERNEL void bn_apply_rows(const T* __restrict__ x, const T* __restrict__ res,
+                              T* __restrict__ y, const float* __restrict__ mean,
+                              const float* __restrict__ rstd,
+                              const float* __restrict__ w,
+                              const float* __restrict__ b, u32 total, u32 C,
+                              u32 Cv, u32 P) {
+  constexpr int V = VecIO<T>::V;
+  const RowLane l = row_lane<V>(Cv, P);
+  if (!l.on) return;
+  float sc[V], mu[V], sh[V], v[V], r[V];
+  chan_get<V>(mean + l.c0, mu);
+  chan_get<V>(rstd + l.c0, sc);
+  chan_get<V>(w + l.c0, v);
+  chan_get<V>(b + l.c0, sh);
+  #pragma unroll
+  for (int j = 0; j < V; ++j) sc[j] = v[j] * sc[j];
+  const u32 step = gridDim.x * P * C;
+  #pragma unroll 2
+  for (u32 off = (blockIdx.x * P + l.p) * C + l.c0; off < total; off += step) {
+    VecIO<T>::load(x + off, v);
+    if (ADD) VecIO<T>::load(res + off, r);
+    #pragma unroll
+    for (int j = 0; j < V; ++j) {
+      // as bn_apply_fast: subtract the mean first
+      float o = (v[j] - mu[j]) * sc[j] + sh[j];
+      if (ADD) o += r[j];
+      if (RELU) o = fmaxf(o, 0.f);
+      v[j] = o;
+    }
+    VecIO<T>::store(y + off, v);
+  }
+}
+
+// backward reductions, pixel ranges as in stats_rows: g = dy gated by y > 0;
+// dbeta += g; dgamma += g * xhat; optionally write g out
+template <typename T, bool RELU, bool WRITE_G>
+TFOSR_ROWS_KERNEL void bwd_stats_rows(const T* __restrict__ x, const T* __restrict__ dy,
+                               const T* __restrict__ y, T* __restrict__ gout,
+                               const float* __restrict__ mean,
+                               const float* __restrict__ rstd,
+                               float* __restrict__ partials, u32 M, u32 C,
+                               u32 Cv, u32 P, u32 ppb) {
+  extern __shared__ float lds[];  // [P][2C]
+  constexpr int V = VecIO<T>::V;
+  const RowLane l = row_lane<V>(Cv, P);
+  float sg[V], sb[V], mu[V], rs[V], xv[V], dv[V], yv[V];
+  #pragma unroll
+  for (int j = 0; j < V; ++j) { sg[j] = 0.f; sb[j] = 0.f; }
+  const u32 m0 = blockIdx.x * ppb;
+  const u32 m1 = m0 + ppb < M ? m0 + ppb : M;
+  if (l.on) {
+    chan_get<V>(mean + l.c0, mu);
+    chan_get<V>(rstd + l.c0, rs);
+    const u32 end = m1 * C, step = P * C;
+    #pragma unroll 2
+    for (u32 off = (m0 + l.p) * C + l.c0; off < end; off += step) {
+      VecIO<T>::load(x + off, xv);
+      VecIO<T>::load(dy + off, dv);
+      if (RELU) VecIO<T>::load(y + off, yv);
+      #pragma unroll
+      for (int j = 0; j < V; ++j) {
+        float g = RELU ? (yv[j] > 0.f ? dv[j] : 0.f) : dv[j];
+        sb[j] += g;
+        sg[j] += g * (xv[j] - mu[j]) * rs[j];
+        dv[j] = g;
+      }
+      if (WRITE_G) VecIO<T>::store(gout + off, dv);
+    }
+  }
+  rows_reduce<V>(sg, sb, lds, l, C, P);
+  if (l.on && l.p == 0) {
+    float* out = partials + (size_t)blockIdx.x * 2 * C + l.c0;
+    vec_put<V>(out, sg);
+    vec_put<V>(out + C, sb);
+  }
+}
+
+// dx as bwd_dx_fast computes it, pixel groups as in bn_apply_rows
+template <typename T, bool RELU>
+TFOSR_ROWS_KERNEL void bwd_dx_rows(const T* __restrict__ x, const T* __restrict__ dy,
+                            const T* __restrict__ y, T* __restrict__ dx,
+                            const float* __restrict__ mean,
+                            const float* __restrict__ rstd,
+                            const float* __restrict__ w,
+                            const float* __restrict__ dg,
+                            const float* __restrict__ db, u32 total, u32 C,
+                            u32 Cv, u32 P, float invM) {
+  constexpr int V = VecIO<T>::V;
+  const RowLane l = row_lane<V>(Cv, P);
+  if (!l.on) return;
+  float sc[V], mu[V], rs[V], dgm[V], dbm[V], xv[V], dv[V], yv[V];
+  chan_get<V>(mean + l.c0, mu);
+  chan_get<V>(rstd + l.c0, rs);
+  chan_get<V>(w + l.c0, sc);
+  chan_get<V>(dg + l.c0, dgm);
+  chan_get<V>(db + l.c0, dbm);
+  #pragma unroll
+  for (int j = 0; j < V; ++j) {
+    sc[j] = sc[j] * rs[j];
+    dgm[j] = dgm[j] * invM;
+    dbm[j] = dbm[j] * invM;
+  }
+  const u32 step = gridDim.x * P * C;
+  #pragma unroll 2
+  for (u32 off = (blockIdx.x * P + l.p) * C + l.c0; off < total; off += step) {
+    VecIO<T>::load(x + off, xv);
+    VecIO<T>::load(dy + off, dv);
+    if (RELU) VecIO<T>::load(y + off, yv);
+    #pragma unroll
+    for (int j = 0; j < V; ++j) {
+      float g = RELU ? (yv[j] > 0.f ? dv[j] : 0.f) : dv[j];
+      float xhat = (xv[j] - mu[j]) * rs[j];
+      dv[j] = sc[j] * (g - dbm[j] - xhat * dgm[j]);
+    }
+    VecIO<T>::store(dx + off, dv);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Generic fallbacks (any layout/shape): scalar, 64-bit safe
 // ---------------------------------------------------------------------------
 
@@ -758,22 +1037,109 @@ static inline int red_grid(long nvec, int quantum) {
   return (int)g;
 }
 
+extern "C" int tfosr_bn_rows_mode();
+
+// The row tier's launch shape; nb == 0 => the shape is not this tier's.
+struct RowsPlan {
+  int nb;       // reduction blocks = rows of the partials workspace
+  int P;        // pixel lanes
+  int threads;  // block size: a multiple of 64, P * Cv of them at work
+  u32 ppb;      // pixels per reduction block, a multiple of P
+};
+
+static RowsPlan rows_plan(long total, int C, int vec, int is_nhwc);
+
+// The reduction launchers get nb from the caller and work the plan out again:
+// the two must agree (same shape, same TFOS_BN_ROWS), or the launch would have
+// a shape the workspace was not sized for.
+static RowsPlan rows_plan_for(int nb, long total, int C, int vec, int is_nhwc) {
+  const RowsPlan r = rows_plan(total, C, vec, is_nhwc);
+  if (r.nb != nb) {
+    fprintf(stderr, "bn rows: caller's nb %d is not the plan's %d\n", nb, r.nb);
+    abort();
+  }
+  return r;
+}
+
+static RowsPlan rows_plan(long total, int C, int vec, int is_nhwc) {
+  RowsPlan r = {0, 0, 0, 0};
+  if (tfosr_bn_rows_mode() != 1 || !is_nhwc || total <= 0 ||
+      total >= (1L << 31) || C % vec != 0 || C / vec > 256 ||
+      fast_ok(is_nhwc, total, C, vec))
+    return r;
+  const int Cv = C / vec;
+  // the block size with the smallest share of idle lanes, the larger on a tie
+  int idle = 0;
+  for (int t = 64; t <= 256; t += 64) {
+    if (t < Cv) continue;
+    if (r.threads == 0 || (t % Cv) * r.threads <= idle * t) {
+      r.threads = t;
+      idle = t % Cv;
+    }
+  }
+  r.P = r.threads / Cv;
+  // red_grid's policy: >= 32 vectors per thread keeps the partials a few
+  // percent of the tensor, [64, 1024] keeps the chip busy on small layers;
+  // never more blocks than groups of P pixels
+  const long M = total / C;
+  long g = total / vec / (r.threads * 32);
+  if (g < 64) g = 64;
+  if (g > 1024) g = 1024;
+  const long groups = (M + r.P - 1) / r.P;
+  if (g > groups) g = groups;
+  long ppb = (M + g - 1) / g;
+  ppb = (ppb + r.P - 1) / r.P * r.P;
+  r.ppb = (u32)ppb;
+  r.nb = (int)((M + ppb - 1) / ppb);
+  return r;
+}
+
 extern "C" {
 
-// #blocks the two-stage fast reduction will use; 0 => generic path
-// (caller sizes the partials workspace as max(nb,1) * 2C floats and must
-// ZERO it when nb == 0)
+// TFOS_BN_ROWS: 1 on (default), 0 off (the generic kernels), -1 anything else
+int tfosr_bn_rows_mode() {
+  const char* e = getenv("TFOS_BN_ROWS");
+  if (!e || !*e || !strcmp(e, "on")) return 1;
+  if (!strcmp(e, "off")) return 0;
+  return -1;
+}
+
+// #blocks the two-stage fast reduction will use; 0 => not the fast path
 int tfosr_bn_fast_blocks(long total, int C, int is_bf16, int is_nhwc) {
   int vec = is_bf16 ? 8 : 4;
   if (!fast_ok(is_nhwc, total, C, vec)) return 0;
   return red_grid(total / vec, grid_quantum(C, vec));
 }
 
+// #blocks of the row tier's reductions, with its pixel lanes and block size;
+// 0 => not the row tier. The caller hands the launchers nb = the fast blocks
+// or else these, and sizes the partials workspace as max(nb, 1) * 2C floats,
+// which it must ZERO when nb == 0 (the generic path).
+int tfosr_bn_rows_plan(long total, int C, int is_bf16, int is_nhwc,
+                       int* pixel_lanes, int* threads) {
+  const RowsPlan r = rows_plan(total, C, is_bf16 ? 8 : 4, is_nhwc);
+  *pixel_lanes = r.P;
+  *threads = r.threads;
+  return r.nb;
+}
+
 void tfosr_bn_stats(const void* x, int is_bf16, int is_nhwc, float* partials,
                     int nb, int N, int C, long HW, hipStream_t s) {
   const long total = (long)N * HW * C;
+  const int vec = is_bf16 ? 8 : 4;
+  if (nb > 0 && !fast_ok(is_nhwc, total, C, vec)) {
+    const RowsPlan r = rows_plan_for(nb, total, C, vec, is_nhwc);
+    const u32 M = (u32)(total / C);
+    const u32 nshift = M < TFOSR_BN_SHIFT_PIXELS ? M : TFOSR_BN_SHIFT_PIXELS;
+    size_t lds = (size_t)r.P * 2 * C * sizeof(float);
+#define SR(T) hipLaunchKernelGGL(stats_rows<T>, dim3(r.nb), dim3(r.threads), \
+                                 lds, s, (const T*)x, partials, M, (u32)C, \
+                                 (u32)(C / vec), (u32)r.P, r.ppb, nshift)
+    if (is_bf16) SR(bf16_t); else SR(float);
+#undef SR
+    return;
+  }
   if (nb > 0) {
-    int vec = is_bf16 ? 8 : 4;
     u32 nvec = (u32)(total / vec);
     size_t lds = 2 * (size_t)C * sizeof(float);
     if (is_bf16)
@@ -798,9 +1164,12 @@ void tfosr_bn_finalize(const float* partials, int nb, const void* x,
                        int is_bf16, int is_nhwc, long HW, float* save_mean,
                        float* save_rstd, float* running_mean, float* running_var,
                        long M, int C, float momentum, float eps, hipStream_t s) {
+  // the shift stage A took: the first pixel on the fast path, the mean of the
+  // first 32 in the row and generic tiers
+  const bool fast = nb > 0 && fast_ok(is_nhwc, M * C, C, is_bf16 ? 8 : 4);
   hipLaunchKernelGGL(stats_merge_finalize, dim3(C), dim3(256), 0, s,
                      partials, nb > 0 ? nb : 1, (u32)C, x, is_bf16, is_nhwc, HW,
-                     nb > 0 ? 1 : (int)(M < TFOSR_BN_SHIFT_PIXELS ? M : TFOSR_BN_SHIFT_PIXELS),
+                     fast ? 1 : (int)(M < TFOSR_BN_SHIFT_PIXELS ? M : TFOSR_BN_SHIFT_PIXELS),
                      save_mean, save_rstd,
                      running_mean, running_var, M, momentum, eps);
 }
@@ -853,6 +1222,23 @@ void tfosr_bn_apply(const void* x, const void* res, void* y, unsigned char* mask
 #undef APPLY_FAST
     return;
   }
+  const RowsPlan rp = rows_plan(total, C, vec, is_nhwc);
+  if (rp.nb > 0) {
+    int grid = tfosr_grid(total / C, rp.P);
+#define APPLY_ROWS(T, R, A) \
+    hipLaunchKernelGGL((bn_apply_rows<T, R, A>), dim3(grid), dim3(rp.threads), \
+                       0, s, (const T*)x, (const T*)res, (T*)y, mean, rstd, w, \
+                       b, (u32)total, (u32)C, (u32)(C / vec), (u32)rp.P)
+    if (is_bf16) {
+      if (relu) { if (add) APPLY_ROWS(bf16_t, true, true); else APPLY_ROWS(bf16_t, true, false); }
+      else      { if (add) APPLY_ROWS(bf16_t, false, true); else APPLY_ROWS(bf16_t, false, false); }
+    } else {
+      if (relu) { if (add) APPLY_ROWS(float, true, true); else APPLY_ROWS(float, true, false); }
+      else      { if (add) APPLY_ROWS(float, false, true); else APPLY_ROWS(float, false, false); }
+    }
+#undef APPLY_ROWS
+    return;
+  }
   int grid = tfosr_grid(total, 256);
 #define APPLY_GEN(T, L, R, A) \
   hipLaunchKernelGGL((bn_apply_generic<T, L, R, A>), dim3(grid), dim3(256), 0, s, \
@@ -881,8 +1267,26 @@ void tfosr_bn_bwd_stats(const void* x, const void* dy, const void* y,
                         long HW, hipStream_t s) {
   const long total = (long)N * HW * C;
   const bool wg = gout != nullptr;
+  const int vec = is_bf16 ? 8 : 4;
+  if (nb > 0 && !fast_ok(is_nhwc, total, C, vec)) {
+    const RowsPlan r = rows_plan_for(nb, total, C, vec, is_nhwc);
+    size_t lds = (size_t)r.P * 2 * C * sizeof(float);
+#define BS_ROWS(T, R, W) \
+    hipLaunchKernelGGL((bwd_stats_rows<T, R, W>), dim3(r.nb), dim3(r.threads), \
+                       lds, s, (const T*)x, (const T*)dy, (const T*)y, \
+                       (T*)gout, mean, rstd, partials, (u32)(total / C), \
+                       (u32)C, (u32)(C / vec), (u32)r.P, r.ppb)
+    if (is_bf16) {
+      if (relu) { if (wg) BS_ROWS(bf16_t, true, true); else BS_ROWS(bf16_t, true, false); }
+      else      { if (wg) BS_ROWS(bf16_t, false, true); else BS_ROWS(bf16_t, false, false); }
+    } else {
+      if (relu) { if (wg) BS_ROWS(float, true, true); else BS_ROWS(float, true, false); }
+      else      { if (wg) BS_ROWS(float, false, true); else BS_ROWS(float, false, false); }
+    }
+#undef BS_ROWS
+    return;
+  }
   if (nb > 0) {
-    int vec = is_bf16 ? 8 : 4;
     u32 nvec = (u32)(total / vec);
     size_t lds = 2 * (size_t)C * sizeof(float);
 #define BS_FAST(T, R, W) \
@@ -943,6 +1347,19 @@ void tfosr_bn_bwd_dx(const void* x, const void* dy, const void* y,
     if (is_bf16) { if (relu) DX_FAST(bf16_t, true); else DX_FAST(bf16_t, false); }
     else { if (relu) DX_FAST(float, true); else DX_FAST(float, false); }
 #undef DX_FAST
+    return;
+  }
+  const RowsPlan rp = rows_plan(total, C, vec, is_nhwc);
+  if (rp.nb > 0) {
+    int grid = tfosr_grid(total / C, rp.P);
+#define DX_ROWS(T, R) \
+    hipLaunchKernelGGL((bwd_dx_rows<T, R>), dim3(grid), dim3(rp.threads), 0, s, \
+                       (const T*)x, (const T*)dy, (const T*)y, (T*)dx, mean, \
+                       rstd, w, dg, db, (u32)total, (u32)C, (u32)(C / vec), \
+                       (u32)rp.P, invM)
+    if (is_bf16) { if (relu) DX_ROWS(bf16_t, true); else DX_ROWS(bf16_t, false); }
+    else { if (relu) DX_ROWS(float, true); else DX_ROWS(float, false); }
+#undef DX_ROWS
     return;
   }
   int grid = tfosr_grid(total, 256);

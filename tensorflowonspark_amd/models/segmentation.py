@@ -7,8 +7,9 @@ with 3 mask classes (reference ``examples/segmentation/segmentation_spark.py:68-
 backbone) configuration named by BASELINE.json config 5 (bf16, 8x MI355X,
 large-activation path).
 
-Both route BN+ReLU through the fused CDNA4 kernels; widths that divide 2048
-hit the fast reduction path.
+Both route BatchNorm (+ReLU, +residual) through the fused CDNA4 kernels:
+widths that divide 2048 hit the fast reduction path, the MobileNetV2 encoder's
+other widths (24 .. 960) the vectorised row tier.
 """
 
 import torch
@@ -16,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops.modules import (ConvTranspose2dMFMA, DepthwiseConv3x3,
-                           DilatedConv3x3, FusedBNReLU)
+                           DilatedConv3x3, FusedBN, FusedBNAdd, FusedBNReLU)
 from .resnet import Bottleneck, ResNet, _maybe_pack_weights
 
 
@@ -51,13 +52,42 @@ class InvertedResidual(nn.Module):
         layers += [
             ConvBNReLU(hidden, hidden, k=3, stride=stride, groups=hidden),
             nn.Conv2d(hidden, cout, 1, bias=False),
-            nn.BatchNorm2d(cout),
+            # the project BN is linear; with a skip it adds the block input in
+            # the same pass (same parameter and buffer names as BatchNorm2d)
+            FusedBNAdd(cout) if self.use_res else FusedBN(cout),
         ]
         self.conv = nn.Sequential(*layers)
 
     def forward(self, x):
+        if not self.use_res:
+            return self.conv(x)
+        out = x
+        last = len(self.conv) - 1
+        for i in range(last):
+            out = self.conv[i](out)
+        return self.conv[last](out, x.to(out.dtype))
+
+
+class _PlainInvertedResidual(nn.Module):
+    """Scriptable clone of InvertedResidual: the same children under the same
+    names, the project BN as a plain BatchNorm2d and the skip as an add."""
+
+    def __init__(self, blk):
+        super().__init__()
+        from ..ops.modules import _SCRIPT_CLONE_KEEPALIVE, _bn_clone
+        _SCRIPT_CLONE_KEEPALIVE.append(blk)
+        layers = list(blk.conv)
+        self.use_res = blk.use_res
+        self.conv = nn.Sequential(*layers[:-1], _bn_clone(layers[-1]))
+        self.train(blk.training)
+
+    def forward(self, x):
         out = self.conv(x)
         return x + out if self.use_res else out
+
+
+InvertedResidual.__prepare_scriptable__ = \
+    lambda self: _PlainInvertedResidual(self)
 
 
 class MobileNetV2Encoder(nn.Module):

@@ -224,6 +224,13 @@ class FusedBNAddReLU(FusedBNReLU):
     ADD = True
 
 
+class FusedBNAdd(FusedBNReLU):
+    """y = bn(x) + residual — the linear-bottleneck tail of a MobileNetV2
+    block as one op; backward hands dy on as the residual gradient."""
+    RELU = False
+    ADD = True
+
+
 # ---------------------------------------------------------------------------
 # Fused softmax cross-entropy (sparse labels, ignore_index, label smoothing)
 # ---------------------------------------------------------------------------
@@ -1735,8 +1742,29 @@ def _fusedbn_prepare(self):
     return bn
 
 
+class _PlainBNAdd(nn.BatchNorm2d):
+    """Scriptable FusedBNAdd: BatchNorm2d's parameters and buffers under the
+    same names, forward(x, res) = bn(x) + res."""
+
+    def forward(self, x, res):
+        y = F.batch_norm(x, self.running_mean, self.running_var, self.weight,
+                         self.bias, self.training, self.momentum, self.eps)
+        return y + res
+
+
+def _fusedbn_add_prepare(self):
+    _SCRIPT_CLONE_KEEPALIVE.append(self)
+    out = _PlainBNAdd(self.num_features, eps=self.eps, momentum=self.momentum)
+    out.load_state_dict(self.state_dict())
+    out.train(self.training)
+    return out
+
+
 # FusedBNAddReLU takes (x, res) — its parents (the residual blocks) provide
-# their own scriptable clones below, so only the one-arg variants get hooks.
+# their own scriptable clones below, so it gets no hook of its own. FusedBNAdd
+# has one (_fusedbn_add_prepare) so that it scripts where it is used on its
+# own; inside InvertedResidual the block's clone replaces it first, with a
+# plain BatchNorm2d and the add in the block, which keeps conv.N.* a plain BN.
 def _maxpool_prepare(self):
     _SCRIPT_CLONE_KEEPALIVE.append(self)
     return nn.MaxPool2d(self.k, self.s, self.p)
@@ -1745,6 +1773,7 @@ def _maxpool_prepare(self):
 FusedMaxPool2d.__prepare_scriptable__ = _maxpool_prepare
 FusedBNReLU.__prepare_scriptable__ = _fusedbn_prepare
 FusedBN.__prepare_scriptable__ = _fusedbn_prepare
+FusedBNAdd.__prepare_scriptable__ = _fusedbn_add_prepare
 Conv1x1.__prepare_scriptable__ = lambda self: _conv_clone(self)
 Conv3x3.__prepare_scriptable__ = lambda self: _conv_clone(self)
 StemConv7x7.__prepare_scriptable__ = lambda self: _conv_clone(self)

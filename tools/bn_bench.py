@@ -27,13 +27,19 @@ the conv kernel followed by the statistics pass against the conv kernel with
 the statistics epilogue followed by the tile merge (see ``epilogue_main``); it
 is what the ``TFOS_BN_EPI=auto`` rule in ops/modules.py was read off.
 
+``--rows`` is a third table: per BatchNorm of the U-Net (MobileNetV2 encoder)
+whose width takes the NHWC row tier, each kernel family with ``TFOS_BN_ROWS``
+on against off (the generic kernels), see ``rows_main``.
+
 The variants timed are the ones the ResNet-50 step runs most: stats; apply
 with ReLU (and with ReLU + residual, ``apply+res``); bwd stats with the mask
 (and writing the gated gradient, ``bwd stats+g``); bwd dx with the mask.
 """
 
 import argparse
+import collections
 import importlib.util
+import json
 import os
 import statistics
 import sys
@@ -218,6 +224,118 @@ def epilogue_main(args):
           "new where ahead {:.3f}".format(step_old, step_new, step_auto))
 
 
+def unet_bn_shapes(ext, batch, bf16):
+    """(C, H, W, relu, add) -> count over the U-Net's fused BatchNorms that
+    take the row tier at this batch, from a CPU forward of the model."""
+    from tensorflowonspark_amd.models import unet_mobilenet
+    from tensorflowonspark_amd.ops.modules import FusedBNReLU
+    model = unet_mobilenet().eval()
+    seen = collections.Counter()
+
+    def hook(m, args, out):
+        _, C, H, W = out.shape
+        if ext.bn_rows_plan(batch * C * H * W, C, bf16, True)[0] > 0:
+            seen[(C, H, W, m.RELU, m.ADD)] += 1
+
+    for m in model.modules():
+        if isinstance(m, FusedBNReLU):
+            m.register_forward_hook(hook)
+    with torch.no_grad():
+        model(torch.zeros(1, 3, 128, 128))
+    return sorted(seen.items())
+
+
+def rows_main(args):
+    """--rows: per row-tier BatchNorm of the U-Net at 128x128, the four kernel
+    families as that layer runs them (ReLU gated on y; the project BN of a
+    skip block adds the residual and writes the gated gradient), with
+    TFOS_BN_ROWS=on and =off alternating inside every round on the same
+    tensors. Columns: medians over the rounds in ms and GB/s of the bytes the
+    launch must move, the spread (max - min) of off, off/on, and the plain
+    device copy of the same tensor as the yardstick. ``on`` counts as slower
+    only where on - off exceeds off's own spread."""
+    from tensorflowonspark_amd.ops import get_ext
+    ext = get_ext(required=True)
+    bf16 = args.dtype == "bf16"
+    dtype = torch.bfloat16 if bf16 else torch.float32
+    esize = 2 if bf16 else 4
+    N, dev = args.batch, "cuda"
+    os.environ["TFOS_BN_ROWS"] = "on"
+    shapes = unet_bn_shapes(ext, N, bf16)
+    for key, n in shapes:
+        print("# C={} H={} W={} relu={} add={} x{}".format(*key, n))
+    print("batch {} {}: U-Net row-tier BatchNorms, median of {} rounds x {} "
+          "launches".format(N, args.dtype, args.rounds, args.iters))
+    print("{:>4s} {:>3s} {:>2s} {:<8s} {:<10s} {:>6s} {:>9s} | {:>8s} {:>7s} "
+          "{:>7s} | {:>8s} {:>7s} | {:>6s}".format(
+              "C", "H", "n", "layer", "kernel", "MB", "copy GB/s", "off ms",
+              "GB/s", "spread", "on ms", "GB/s", "off/on"))
+    records, slower = [], []
+    step = {"on": 0.0, "off": 0.0}
+    for (C, H, W, relu, add), count in shapes:
+        shape = (N, C, H, W)
+
+        def act():
+            return torch.randn(shape, device=dev).to(dtype).contiguous(
+                memory_format=torch.channels_last)
+
+        x, other, y, out = act(), act(), act(), act()
+        vecs = [torch.rand(C, device=dev) + 0.5 for _ in range(5)]
+        nb = ext.bn_rows_plan(x.numel(), C, bf16, True)[0]
+        ws = torch.zeros(nb * 2 * C, device=dev)
+        t = x.numel() * esize
+        st = ext.bn_stage
+        g = out if add else None
+        calls = [
+            ("stats", t, lambda: st(0, x, None, None, None, ws, [], False)),
+            ("apply", (3 if add else 2) * t,
+             lambda: st(1, x, other if add else None, out, None, ws, vecs[:4],
+                        relu)),
+            ("bwd stats", (2 + relu + add) * t,
+             lambda: st(2, x, other, g, None, ws, vecs[:2], relu, y)),
+            ("bwd dx", (3 + relu) * t,
+             lambda: st(3, x, other, out, None, ws, vecs, relu, y)),
+        ]
+        copy = statistics.median(
+            [time_round(lambda: out.copy_(x), args.iters)
+             for _ in range(args.rounds + 1)][1:])
+        layer = ("relu" if relu else "lin") + ("+res" if add else "")
+        for kernel, nbytes, fn in calls:
+            ms = {"off": [], "on": []}
+            for mode in ms:                      # warm up both tiers
+                os.environ["TFOS_BN_ROWS"] = mode
+                fn()
+            torch.cuda.synchronize()
+            for _ in range(args.rounds):
+                for mode in ms:                  # alternate inside a round
+                    os.environ["TFOS_BN_ROWS"] = mode
+                    ms[mode].append(time_round(fn, args.iters))
+            med = {m: statistics.median(v) for m, v in ms.items()}
+            spread = max(ms["off"]) - min(ms["off"])
+            for m in med:
+                step[m] += count * med[m]
+            if med["on"] - med["off"] > spread:
+                slower.append((C, H, layer, kernel))
+            records.append({"batch": N, "C": C, "H": H, "W": W,
+                            "layer": layer, "count": count, "kernel": kernel,
+                            "bytes": nbytes, "copy_ms": copy,
+                            "off_ms": ms["off"], "on_ms": ms["on"]})
+            print("{:4d} {:3d} {:2d} {:<8s} {:<10s} {:6.0f} {:9.0f} | {:8.4f} "
+                  "{:7.0f} {:7.4f} | {:8.4f} {:7.0f} | {:6.2f}".format(
+                      C, H, count, layer, kernel, t / 1e6, 2 * t / copy / 1e6,
+                      med["off"], nbytes / med["off"] / 1e6, spread,
+                      med["on"], nbytes / med["on"] / 1e6,
+                      med["off"] / med["on"]), flush=True)
+        del x, other, y, out, calls
+    os.environ["TFOS_BN_ROWS"] = "on"
+    print("per step (count x medians), ms: off {:.3f}  on {:.3f}".format(
+        step["off"], step["on"]))
+    print("on slower than off beyond off's spread: {}".format(slower or "none"))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(records, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -229,9 +347,15 @@ def main():
     ap.add_argument("--epilogue", action="store_true",
                     help="per ResNet-50 (conv, BN) pair: statistics from the "
                          "conv epilogue vs the separate pass")
+    ap.add_argument("--rows", action="store_true",
+                    help="per U-Net row-tier BatchNorm: TFOS_BN_ROWS on vs off")
+    ap.add_argument("--json", metavar="PATH",
+                    help="with --rows: also write every round's times here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bn_bench needs a GPU")
+    if args.rows:
+        return rows_main(args)
     if args.epilogue:
         return epilogue_main(args)
     from tensorflowonspark_amd.ops import get_ext
