@@ -77,6 +77,15 @@ void tfosr_dwconv3x3_dgrad(const void*, const float*, void*, int, int, int, int,
                            int, int, int, int, hipStream_t);
 void tfosr_dwconv3x3_wrw(const void*, const void*, float*, float*, int, int,
                          int, int, int, int, int, int, hipStream_t);
+void tfosr_convt_head_info(int*, int*, int*, int*, int*, int*, int*, int*, int*,
+                           int*);
+void tfosr_convt_head_wrw_plan(long, int, int, int*, long*);
+void tfosr_convt_head_fwd(const void*, const float*, const float*, void*, int,
+                          int, int, int, int, hipStream_t);
+void tfosr_convt_head_dgrad(const void*, const float*, void*, int, int, int,
+                            int, int, hipStream_t);
+void tfosr_convt_head_wrw(const void*, const void*, float*, float*, float*,
+                          int, int, int, int, int, hipStream_t);
 void tfosr_conv3x3(const void*, const void*, const void*, void*, int, int, int,
                    int, int, int, int, int, int, int, hipStream_t);
 void tfosr_conv_mfma(const void*, const void*, const void*, void*, int, int,
@@ -1076,7 +1085,7 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 8
+#define TFOSR_API_VERSION 9
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
@@ -1301,6 +1310,129 @@ static at::Tensor dwconv3x3_wrw(at::Tensor dy, at::Tensor x, long stride) {
                       dw.data_ptr<float>(), x.scalar_type() == at::kBFloat16,
                       N, C, H, W, OH, OW, stride, cur_stream());
   return dw;
+}
+
+// ---------------------------------------------------------------------------
+// Transposed-conv head (csrc/convt_head.hip): k4 s2 p1, Cin % 8 == 0 in
+// [8, 256], Cout in [1, 8], bf16 channels_last
+// ---------------------------------------------------------------------------
+
+// An activation or gradient as the kernels take it. Returns true when the
+// tensor is empty (nothing to launch).
+static bool cth_check_act(const char* op, const char* name,
+                          const at::Tensor& t) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.dim() == 4, op, ": ", name, " must be 4-D (N, C, H, W), got ",
+              t.dim(), "-D");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, op, ": ", name,
+              " must be bf16, got ", t.scalar_type());
+  if (t.numel() == 0) return true;
+  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name,
+              " must be channels_last-contiguous");
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+              " must be 16-byte aligned");
+  TORCH_CHECK(t.numel() < (1L << 31), op, ": ", name, " has ", t.numel(),
+              " elements, more than the kernels index");
+  return false;
+}
+
+static void cth_check_channels(const char* op, long Cin, long Cout) {
+  TORCH_CHECK(Cin % 8 == 0 && Cin >= 8 && Cin <= 256, op, ": Cin=", Cin,
+              " must be a multiple of 8 in [8, 256]");
+  TORCH_CHECK(Cout >= 1 && Cout <= 8, op, ": Cout=", Cout,
+              " must be in [1, 8]");
+}
+
+static void cth_check_weight(const char* op, const at::Tensor& w,
+                             const at::Tensor& act) {
+  TORCH_CHECK(w.device() == act.device(), op, ": weight must be on ",
+              act.device(), ", got ", w.device());
+  TORCH_CHECK(w.scalar_type() == at::kFloat && w.dim() == 4 &&
+                  w.size(2) == 4 && w.size(3) == 4 && w.is_contiguous(),
+              op, ": weight must be the contiguous fp32 [Cin,Cout,4,4] "
+              "parameter, got ", w.scalar_type(), " ", w.sizes());
+}
+
+static at::Tensor convt_head_fwd(at::Tensor x, at::Tensor w,
+                                 c10::optional<at::Tensor> bias) {
+  const char* op = "convt_head_fwd";
+  const bool empty = cth_check_act(op, "x", x);
+  cth_check_weight(op, w, x);
+  const long N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  const long Cout = w.size(1);
+  TORCH_CHECK(w.size(0) == Cin, op, ": weight must be [Cin,Cout,4,4] with "
+              "Cin=", Cin, ", got ", w.sizes());
+  cth_check_channels(op, Cin, Cout);
+  const float* bp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(bias->device() == x.device() &&
+                    bias->scalar_type() == at::kFloat && bias->dim() == 1 &&
+                    bias->size(0) == Cout && bias->is_contiguous(),
+                op, ": bias must be the contiguous fp32 [Cout] parameter on ",
+                x.device(), " with Cout=", Cout, ", got ",
+                bias->scalar_type(), " ", bias->sizes(), " on ",
+                bias->device());
+    bp = bias->data_ptr<float>();
+  }
+  auto y = at::empty({N, Cout, 2 * H, 2 * W}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  if (empty) return y;
+  TORCH_CHECK(y.numel() < (1L << 31), op, ": y has ", y.numel(),
+              " elements, more than the kernels index");
+  tfosr_convt_head_fwd(x.data_ptr(), w.data_ptr<float>(), bp, y.data_ptr(), N,
+                       Cin, Cout, H, W, cur_stream());
+  return y;
+}
+
+static at::Tensor convt_head_dgrad(at::Tensor dy, at::Tensor w, long H,
+                                   long W) {
+  const char* op = "convt_head_dgrad";
+  const bool empty = cth_check_act(op, "dy", dy);
+  cth_check_weight(op, w, dy);
+  TORCH_CHECK(H >= 0 && W >= 0, op, ": H and W must not be negative");
+  const long N = dy.size(0), Cout = dy.size(1), Cin = w.size(0);
+  TORCH_CHECK(w.size(1) == Cout, op, ": weight must be [Cin,Cout,4,4] with "
+              "Cout=", Cout, ", got ", w.sizes());
+  cth_check_channels(op, Cin, Cout);
+  TORCH_CHECK(dy.size(2) == 2 * H && dy.size(3) == 2 * W, op, ": a ", H, "x",
+              W, " input gives ", 2 * H, "x", 2 * W, ", the gradient is ",
+              dy.size(2), "x", dy.size(3));
+  auto dx = at::empty({N, Cin, H, W}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  if (empty || dx.numel() == 0) return dx;
+  TORCH_CHECK(dx.numel() < (1L << 31), op, ": dx has ", dx.numel(),
+              " elements, more than the kernels index");
+  tfosr_convt_head_dgrad(dy.data_ptr(), w.data_ptr<float>(), dx.data_ptr(), N,
+                         Cin, Cout, H, W, cur_stream());
+  return dx;
+}
+
+static std::tuple<at::Tensor, at::Tensor> convt_head_wrw(at::Tensor dy,
+                                                         at::Tensor x) {
+  const char* op = "convt_head_wrw";
+  const bool dy_empty = cth_check_act(op, "dy", dy);
+  const bool x_empty = cth_check_act(op, "x", x);
+  TORCH_CHECK(x.device() == dy.device(), op, ": x must be on ", dy.device(),
+              ", got ", x.device());
+  const long N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  const long Cout = dy.size(1);
+  cth_check_channels(op, Cin, Cout);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == 2 * H && dy.size(3) == 2 * W,
+              op, ": x ", x.sizes(), " gives a gradient of [", N, ", Cout, ",
+              2 * H, ", ", 2 * W, "], got ", dy.sizes());
+  auto opts = x.options().dtype(at::kFloat);
+  if (dy_empty || x_empty)
+    return {at::zeros({Cin, Cout, 4, 4}, opts), at::zeros({Cout}, opts)};
+  int nblk;
+  long slab;
+  tfosr_convt_head_wrw_plan(N * H * W, (int)Cin, (int)Cout, &nblk, &slab);
+  auto part = at::empty({(long)nblk, Cin * 16 * Cout + Cout}, opts);
+  auto dw = at::empty({Cin, Cout, 4, 4}, opts);
+  auto db = at::empty({Cout}, opts);
+  tfosr_convt_head_wrw(dy.data_ptr(), x.data_ptr(), part.data_ptr<float>(),
+                       dw.data_ptr<float>(), db.data_ptr<float>(), N, Cin,
+                       Cout, H, W, cur_stream());
+  return {dw, db};
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1711,6 +1843,42 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     d["slab"] = slab;
     return d;
   });
+
+  m.def("convt_head_fwd", &convt_head_fwd, py::arg("x"), py::arg("w"),
+        py::arg("bias") = py::none());
+  m.def("convt_head_dgrad", &convt_head_dgrad, py::arg("dy"), py::arg("w"),
+        py::arg("H"), py::arg("W"));
+  m.def("convt_head_wrw", &convt_head_wrw, py::arg("dy"), py::arg("x"));
+  m.def("convt_head_info", []() {
+    int block, max_grid, fwd_tile, dg_h, dg_w, persist_kb, kstep, min_pix,
+        max_blocks, fin_lanes;
+    tfosr_convt_head_info(&block, &max_grid, &fwd_tile, &dg_h, &dg_w,
+                          &persist_kb, &kstep, &min_pix, &max_blocks,
+                          &fin_lanes);
+    py::dict d;
+    d["block"] = block;
+    d["max_grid"] = max_grid;
+    d["fwd_tile"] = fwd_tile;
+    d["dgrad_tile_h"] = dg_h;
+    d["dgrad_tile_w"] = dg_w;
+    d["w_persist_kb"] = persist_kb;
+    d["wrw_kstep"] = kstep;
+    d["wrw_min_pix"] = min_pix;
+    d["wrw_max_blocks"] = max_blocks;
+    d["fin_lanes"] = fin_lanes;
+    return d;
+  });
+  m.def("convt_head_wrw_plan", [](long M, long Cin, long Cout) {
+    TORCH_CHECK(M > 0 && Cin > 0 && Cout > 0, "convt_head_wrw_plan: M, Cin "
+                "and Cout must be positive");
+    int nblk;
+    long slab;
+    tfosr_convt_head_wrw_plan(M, (int)Cin, (int)Cout, &nblk, &slab);
+    py::dict d;
+    d["nblk"] = nblk;
+    d["slab"] = slab;
+    return d;
+  }, py::arg("M"), py::arg("Cin"), py::arg("Cout"));
 
   // native TFRecord codec (CPU): bulk scan/write with HW CRC32-C
   m.def("crc32c", [](py::bytes data) {

@@ -16,8 +16,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops.modules import (ConvTranspose2dMFMA, DepthwiseConv3x3,
-                           DilatedConv3x3, FusedBN, FusedBNAdd, FusedBNReLU)
+from ..ops.modules import (ConvTranspose2dHead, ConvTranspose2dMFMA,
+                           DepthwiseConv3x3, DilatedConv3x3, FusedBN,
+                           FusedBNAdd, FusedBNReLU)
 from .resnet import Bottleneck, ResNet, _maybe_pack_weights
 
 
@@ -147,8 +148,7 @@ class UNetMobileNet(nn.Module):
         self.up2 = UpBlock(512 + 96, 256)  # 8 -> 16, concat 32 -> 288
         self.up3 = UpBlock(256 + 32, 128)  # 16 -> 32, concat 24 -> 152
         self.up4 = UpBlock(128 + 24, 64)   # 32 -> 64, concat 16 -> 80
-        self.head = nn.ConvTranspose2d(64 + 16, num_classes, 4, stride=2,
-                                       padding=1)
+        self.head = ConvTranspose2dHead(64 + 16, num_classes)
 
     def forward(self, x):
         t2, t4, t8, t16, t32 = self.encoder(x)

@@ -1180,6 +1180,160 @@ class ConvTranspose2dMFMA(nn.Module):
 
 
 # ---------------------------------------------------------------------------
+# Transposed-conv head for few classes (csrc/convt_head.hip)
+# ---------------------------------------------------------------------------
+
+_CTH_DIRECTIONS = ("fwd", "dgrad", "wrw")
+
+
+def _cth_table():
+    """(N, Cin, Cout, H, W, fwd, dgrad, wrw) per measured shape: True where
+    tools/convt_head_bench.py measured the in-tree kernel no slower than the
+    library on the MI355X (docs/performance.md "Transposed-conv head"; the
+    run is profiles/convt_head_bench.json)."""
+    T = True   # no direction lost: 1.6x (dgrad) to 10x (fwd at b1024)
+    return (
+        (64, 80, 3, 64, 64, T, T, T),
+        (1024, 80, 3, 64, 64, T, T, T),
+    )
+
+
+def _cth_auto(direction, N, cin, cout, H, W):
+    """TFOS_CONVT_HEAD=auto policy: is ``direction`` ('fwd', 'dgrad' or
+    'wrw') routed in-tree? A shape that was not measured takes the decision
+    of the measured one whose input element count is nearest in ratio:
+    these are streaming kernels, and how they stand against the library
+    follows the tensor size."""
+    rows = _cth_table()
+    want = float(max(1, N * cin * H * W))
+
+    def dist(r):
+        have = float(r[0] * r[1] * r[3] * r[4])
+        return max(have / want, want / have)
+
+    exact = [r for r in rows if r[:5] == (N, cin, cout, H, W)]
+    row = exact[0] if exact else min(rows, key=dist)
+    return row[5 + _CTH_DIRECTIONS.index(direction)]
+
+
+def _cth_route(N, cin, cout, H, W):
+    """(fwd_in_tree, dgrad_in_tree, wrw_in_tree) for TFOS_CONVT_HEAD, or None
+    for the plain library call."""
+    mode = os.environ.get("TFOS_CONVT_HEAD", "auto")
+    if mode == "miopen":
+        return None
+    if mode == "hip":
+        return True, True, True
+    if mode != "auto":
+        raise ValueError("TFOS_CONVT_HEAD must be auto, hip or miopen, got "
+                         + repr(mode))
+    route = tuple(_cth_auto(d, N, cin, cout, H, W) for d in _CTH_DIRECTIONS)
+    return route if any(route) else None
+
+
+class _ConvTHeadFn(torch.autograd.Function):
+    """ConvTranspose2d k4 s2 p1 with bias on channels_last bf16 with the
+    module's fp32 weight and bias. Each of forward, dgrad and wrw (weight and
+    bias gradient together) runs in-tree or through the library as its flag
+    says; the library sees weight and bias cast to bf16, as under autocast,
+    where the kernels round the weight on load and keep the bias in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, fwd_in_tree, dgrad_in_tree,
+                wrw_in_tree):
+        if fwd_in_tree:
+            y = get_ext(required=True).convt_head_fwd(x, weight, bias)
+        else:
+            y = F.conv_transpose2d(
+                x, weight.to(x.dtype),
+                None if bias is None else bias.to(x.dtype), 2, 1)
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        ctx.in_tree = (dgrad_in_tree, wrw_in_tree)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dgrad_in_tree, wrw_in_tree = ctx.in_tree
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_db = ctx.has_bias and ctx.needs_input_grad[2]
+        # an expanded (stride-0) gradient, as from y.sum().backward(),
+        # becomes a real channels_last tensor here
+        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        dx = dw = db = None
+        if need_dx and dgrad_in_tree:
+            dx = get_ext(required=True).convt_head_dgrad(
+                dy, weight, x.shape[2], x.shape[3])
+        if (need_dw or need_db) and wrw_in_tree:
+            dw, db = get_ext(required=True).convt_head_wrw(dy, x)
+        lib_dx = need_dx and dx is None
+        lib_dw = (need_dw or need_db) and dw is None
+        if lib_dx or lib_dw:
+            gx, gw, gb = torch.ops.aten.convolution_backward(
+                dy, x, weight.to(x.dtype), [weight.shape[1]], [2, 2], [1, 1],
+                [1, 1], True, [0, 0], 1, [lib_dx, lib_dw and need_dw,
+                                          lib_dw and need_db])
+            if lib_dx:
+                dx = gx
+            if lib_dw:
+                dw = gw.to(weight.dtype) if need_dw else None
+                db = gb.to(weight.dtype) if need_db else None
+        return (dx, dw if need_dw else None, db if need_db else None,
+                None, None, None)
+
+
+class ConvTranspose2dHead(nn.ConvTranspose2d):
+    """ConvTranspose2d(cin, cout, 4, stride=2, padding=1) for a segmentation
+    head: many input channels, a handful of classes, with a bias.
+
+    A subclass of nn.ConvTranspose2d so that parameter names, shapes, the
+    default initialisation and the RNG draw order are exactly the library
+    module's. Backend select via TFOS_CONVT_HEAD: 'auto' (default: each of
+    forward, dgrad and wrw goes in-tree only where it was measured no slower
+    than the library, see _cth_auto), 'hip' (all three in-tree), 'miopen'
+    (library call). The kernels take bf16 activations (directly or under bf16
+    autocast) with cin % 8 == 0 in [8, 256] and cout in [1, 8]; fp32
+    activations, CPU tensors and other shapes stay on the library path.
+    """
+
+    def __init__(self, cin, cout, bias=True, device=None, dtype=None):
+        super().__init__(cin, cout, 4, stride=2, padding=1, bias=bias,
+                         device=device, dtype=dtype)
+
+    def forward(self, x, output_size=None):
+        cin, cout = self.in_channels, self.out_channels
+        if x.is_cuda and x.dim() == 4 and output_size is None \
+                and self.weight.dtype == torch.float32:
+            # under autocast the library runs in the autocast dtype whatever
+            # x is; so does this path
+            dt = torch.get_autocast_dtype("cuda") \
+                if torch.is_autocast_enabled("cuda") else x.dtype
+            if dt == torch.bfloat16 and cin % 8 == 0 and 8 <= cin <= 256 \
+                    and 1 <= cout <= 8 and x.numel() > 0:
+                route = _cth_route(x.shape[0], cin, cout, x.shape[2],
+                                   x.shape[3])
+                if route is not None and get_ext(required=True) is not None:
+                    x = x.to(dt).contiguous(memory_format=torch.channels_last)
+                    return _ConvTHeadFn.apply(x, self.weight, self.bias,
+                                              *route)
+        return super().forward(x, output_size)
+
+    def __prepare_scriptable__(self):
+        # the scripter must not compile the routed forward: hand it a plain
+        # transposed conv that shares weight and bias
+        _SCRIPT_CLONE_KEEPALIVE.append(self)
+        new = nn.ConvTranspose2d(self.in_channels, self.out_channels, 4,
+                                 stride=2, padding=1,
+                                 bias=self.bias is not None)
+        new.weight = self.weight
+        if self.bias is not None:
+            new.bias = self.bias
+        new.train(self.training)
+        return new
+
+
+# ---------------------------------------------------------------------------
 # MFMA GEMM (bf16 inputs, fp32 accumulate) for Dense layers / serving
 # ---------------------------------------------------------------------------
 
