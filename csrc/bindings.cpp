@@ -86,8 +86,6 @@ void tfosr_convt_head_dgrad(const void*, const float*, void*, int, int, int,
                             int, int, hipStream_t);
 void tfosr_convt_head_wrw(const void*, const void*, float*, float*, float*,
                           int, int, int, int, int, hipStream_t);
-void tfosr_conv3x3(const void*, const void*, const void*, void*, int, int, int,
-                   int, int, int, int, int, int, int, hipStream_t);
 void tfosr_conv_mfma(const void*, const void*, const void*, void*, int, int,
                      int, int, int, int, int, int, int, int, int, int, int,
                      int, int, hipStream_t);
@@ -1012,10 +1010,70 @@ void sgd_step(at::Tensor p, at::Tensor g, at::Tensor m, double lr, double mu,
                  cur_stream());
 }
 
-at::Tensor gemm_bt(at::Tensor a, at::Tensor b, bool out_bf16) {
-  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(1),
-              "gemm_bt: A[M,K], B[N,K]");
-  TORCH_CHECK(a.scalar_type() == at::kBFloat16 && b.scalar_type() == at::kBFloat16);
+// ---------------------------------------------------------------------------
+// Argument checks of the implicit-GEMM conv family and gemm_bt: the kernels
+// index raw pointers with sizes narrowed to int, so everything they reach is
+// checked here, before any allocation or launch.
+// ---------------------------------------------------------------------------
+
+// An activation, gradient or output: 4-D bf16 channels_last on a GPU, every
+// size in [1, INT_MAX], C a multiple of cmul (exactly cmul where exact).
+void cv_check_act(const char* op, const char* name, const at::Tensor& t,
+                  long cmul, bool exact = false) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.dim() == 4, op, ": ", name, " must be 4-D (N, C, H, W), got ",
+              t.dim(), "-D");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, op, ": ", name,
+              " must be bf16, got ", t.scalar_type());
+  for (int d = 0; d < 4; ++d)
+    TORCH_CHECK(t.size(d) >= 1 && t.size(d) <= INT_MAX, op, ": ", name,
+                " has size ", t.size(d), " in dimension ", d,
+                ", expected 1 to ", INT_MAX);
+  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name,
+              " must be channels_last-contiguous");
+  TORCH_CHECK(exact ? t.size(1) == cmul : t.size(1) % cmul == 0, op, ": ",
+              name, " must have ", exact ? "exactly " : "a multiple of ", cmul,
+              " channels, got ", t.size(1));
+}
+
+// A second tensor of the call lives on the first one's GPU.
+void cv_check_device(const char* op, const char* name, const at::Tensor& t,
+                     const at::Tensor& ref) {
+  TORCH_CHECK(t.device() == ref.device(), op, ": ", name, " must be on ",
+              ref.device(), ", got ", t.device());
+}
+
+// A weight matrix: 2-D bf16 [rows, cols] on the activation's device (every
+// caller passes it 2-D). It need not be contiguous: the entries launch on
+// w.contiguous().
+void cv_check_weight(const char* op, const char* name, const at::Tensor& w,
+                     const at::Tensor& act, long rows, long cols) {
+  cv_check_device(op, name, w, act);
+  TORCH_CHECK(w.scalar_type() == at::kBFloat16, op, ": ", name,
+              " must be bf16, got ", w.scalar_type());
+  TORCH_CHECK(w.dim() == 2 && w.size(0) == rows && w.size(1) == cols, op,
+              ": ", name, " must be [", rows, ", ", cols,
+              "] (output channels x taps * input channels), got ", w.sizes());
+}
+
+// gemm_bt and gemm_bf16: c[M, N] = a[M, K] @ b[N, K]^T, a ragged K padded to
+// a multiple of 32
+at::Tensor gemm_bt_impl(const char* op, at::Tensor a, at::Tensor b,
+                        bool out_bf16) {
+  TORCH_CHECK(a.is_cuda(), op, ": a must be a GPU tensor");
+  cv_check_device(op, "b", b, a);
+  TORCH_CHECK(a.scalar_type() == at::kBFloat16 &&
+                  b.scalar_type() == at::kBFloat16,
+              op, ": a and b must be bf16, got ", a.scalar_type(), " and ",
+              b.scalar_type());
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(1), op,
+              ": expected A[M,K] and B[N,K], got ", a.sizes(), " and ",
+              b.sizes());
+  TORCH_CHECK(a.size(0) >= 1 && b.size(0) >= 1 && a.size(1) >= 1 &&
+                  a.size(0) <= INT_MAX && b.size(0) <= INT_MAX &&
+                  a.size(1) <= INT_MAX - 31,
+              op, ": M, N and K must be in [1, INT_MAX], got A ", a.sizes(),
+              " and B ", b.sizes());
   int M = a.size(0), N = b.size(0), K = a.size(1);
   if (K % 32 != 0) {
     int Kp = (K + 31) / 32 * 32;
@@ -1032,6 +1090,10 @@ at::Tensor gemm_bt(at::Tensor a, at::Tensor b, bool out_bf16) {
   tfosr_gemm_bt(a.data_ptr(), b.data_ptr(), out.data_ptr(), out_bf16, M, N, K,
                 cur_stream());
   return out;
+}
+
+at::Tensor gemm_bt(at::Tensor a, at::Tensor b, bool out_bf16) {
+  return gemm_bt_impl("gemm_bt", a, b, out_bf16);
 }
 
 // -> (c, part, rows_per_tile): c is gemm_bt(a, b, out_bf16=True) bit for bit;
@@ -1067,12 +1129,20 @@ py::tuple gemm_bt_stats(at::Tensor a, at::Tensor b) {
 
 at::Tensor gemm_bf16(at::Tensor a, at::Tensor b) {
   // A[M,K] @ B[K,N]: feed B^T (contiguous [N,K]) to the kernel
-  return gemm_bt(a, b.t().contiguous(), /*out_bf16=*/false);
+  TORCH_CHECK(b.dim() == 2, "gemm_bf16: expected A[M,K] and B[K,N], got ",
+              a.sizes(), " and ", b.sizes());
+  return gemm_bt_impl("gemm_bf16", a, b.t().contiguous(), /*out_bf16=*/false);
 }
 
 at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
-  TORCH_CHECK(a.sizes() == at::IntArrayRef({64, 8}) &&
-              b.sizes() == at::IntArrayRef({64, 8}));
+  TORCH_CHECK(a.is_cuda(), "mfma_probe: a must be a GPU tensor");
+  cv_check_device("mfma_probe", "b", b, a);
+  TORCH_CHECK(a.scalar_type() == at::kShort && b.scalar_type() == at::kShort &&
+                  a.sizes() == at::IntArrayRef({64, 8}) &&
+                  b.sizes() == at::IntArrayRef({64, 8}),
+              "mfma_probe: a and b must be [64, 8] int16 lane fragments, got ",
+              a.scalar_type(), " ", a.sizes(), " and ", b.scalar_type(), " ",
+              b.sizes());
   auto c = at::empty({64, 4}, a.options().dtype(at::kFloat));
   tfosr_mfma_probe(a.contiguous().data_ptr<short>(),
                    b.contiguous().data_ptr<short>(), c.data_ptr<float>(),
@@ -1085,13 +1155,64 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 9
+#define TFOSR_API_VERSION 10
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
 // tensor that fits the device, so a reach capped at 2^20 keeps every such
 // sum far inside the int range.
 static constexpr long kMaxTapReach = 1L << 20;
+
+// Filter geometry of a conv entry: fh x fw taps (at most 49), stride S,
+// padding P, input dilation D in {1, 2}, filter dilation fd (> 1 only with
+// D == 1). S, P and the tap reach are capped at kMaxTapReach for the reason
+// given there.
+static void cv_check_filter(const char* op, long fh, long fw, long S, long P,
+                            long D, long fd) {
+  TORCH_CHECK(fh >= 1 && fw >= 1 && fh * fw <= 49, op,
+              ": the filter must be at least 1x1 with at most 49 taps, got ",
+              fh, "x", fw);
+  TORCH_CHECK(S >= 1 && S <= kMaxTapReach, op, ": stride must be in [1, ",
+              kMaxTapReach, "], got ", S);
+  TORCH_CHECK(P >= 0 && P <= kMaxTapReach, op, ": padding must be in [0, ",
+              kMaxTapReach, "], got ", P);
+  TORCH_CHECK(D == 1 || D == 2, op, ": input dilation D must be 1 or 2, got ",
+              D);
+  TORCH_CHECK(fd >= 1, op, ": filter dilation fd must be >= 1, got ", fd);
+  TORCH_CHECK(fd == 1 || D == 1, op,
+              ": filter dilation fd > 1 requires input dilation D == 1");
+  TORCH_CHECK(fd <= kMaxTapReach && fd * (fh - 1) <= kMaxTapReach &&
+                  fd * (fw - 1) <= kMaxTapReach,
+              op, ": fd, fd*(fh-1) and fd*(fw-1) must be <= ", kMaxTapReach);
+}
+
+// Natural output length of one axis: floor((in_dilated + 2P - reach - 1) / S)
+// + 1, or 0 where the dilated filter does not fit the padded input.
+static long cv_natural_out(long in, long k, long S, long P, long D, long fd) {
+  const long n = (in - 1) * D + 1 + 2 * P - fd * (k - 1) - 1;
+  return n < 0 ? 0 : n / S + 1;
+}
+
+// The output of an implicit-GEMM launch: OH, OW >= 1, oh * S inside int with
+// room for the tap offsets, and the tile count (256-row tiles x the column
+// tiles picked from Cout) inside the int the launcher makes the grid from.
+static void cv_check_out(const char* op, long N, long Cout, long OH, long OW,
+                         long S) {
+  TORCH_CHECK(Cout >= 1 && Cout <= INT_MAX, op,
+              ": the output needs 1 to ", INT_MAX, " channels, got ", Cout);
+  TORCH_CHECK(OH >= 1 && OW >= 1 && OH <= INT_MAX && OW <= INT_MAX, op,
+              ": the output size must be at least 1x1, got ", OH, "x", OW);
+  TORCH_CHECK((OH - 1) * S <= INT_MAX - 4 * kMaxTapReach &&
+                  (OW - 1) * S <= INT_MAX - 4 * kMaxTapReach,
+              op, ": output size ", OH, "x", OW, " times stride ", S,
+              " exceeds the kernels' 32-bit image coordinates");
+  const long bn = Cout >= 192 ? 256 : 128;
+  const long ntn = (Cout + bn - 1) / bn;
+  TORCH_CHECK(OH <= INT_MAX / OW && N <= INT_MAX / (OH * OW) &&
+                  ((N * OH * OW + 255) / 256) <= INT_MAX / ntn,
+              op, ": ", N, "x", OH, "x", OW, " output pixels of ", Cout,
+              " channels exceed the 32-bit pixel and tile counts");
+}
 
 // Which kernel a conv_mfma launch takes (csrc/conv3x3_halo.hip): the halo
 // kernel covers the plain 3x3 stride-1 padding-1 bf16 launch of natural
@@ -1125,37 +1246,19 @@ static ConvTilePlan conv3x3_tile_plan(long N, long H, long W, long Cin,
 static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
     at::Tensor x, at::Tensor wk, long Cout, long fh, long fw, long S, long P,
     long D, long OH, long OW, long fd, bool out_f32, bool stats) {
-  TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
-              "conv_mfma expects channels_last input");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-              wk.scalar_type() == at::kBFloat16);
-  TORCH_CHECK(fh >= 1 && fw >= 1 && fh * fw <= 49, "bad filter dims");
-  TORCH_CHECK(D == 1 || D == 2, "input dilation must be 1 or 2");
-  TORCH_CHECK(fd >= 1, "conv_mfma: filter dilation fd must be >= 1, got ",
-              fd);
-  TORCH_CHECK(fd == 1 || D == 1,
-              "conv_mfma: filter dilation fd > 1 requires input dilation "
-              "D == 1");
-  // ih = oh*S - P + r*fd is computed in int: keep the tap reach far
-  // below 2^31 so it cannot overflow whatever the image size
-  TORCH_CHECK(fd <= kMaxTapReach && fd * (fh - 1) <= kMaxTapReach &&
-                  fd * (fw - 1) <= kMaxTapReach,
-              "conv_mfma: fd, fd*(fh-1) and fd*(fw-1) must be <= ",
-              kMaxTapReach);
+  const char* op = stats ? "conv_mfma_stats" : "conv_mfma";
+  cv_check_act(op, "x", x, 32);
+  cv_check_filter(op, fh, fw, S, P, D, fd);
   long taps = fh * fw;
   int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-  TORCH_CHECK(Cin % 32 == 0, "conv_mfma requires Cin % 32 == 0");
-  TORCH_CHECK(wk.size(1) == taps * Cin);
-  if (OH < 0) {
-    long HV = (H - 1) * D + 1, WV = (W - 1) * D + 1;
-    long nh = HV + 2 * P - fd * (fh - 1) - 1;
-    long nw = WV + 2 * P - fd * (fw - 1) - 1;
-    TORCH_CHECK(nh >= 0 && nw >= 0,
-                "conv_mfma: the dilated filter does not fit the padded "
-                "input");
-    OH = nh / S + 1;
-    OW = nw / S + 1;
+  if (OH < 0) {  // the natural size; an explicit one is the dgrad's input size
+    OH = cv_natural_out(H, fh, S, P, D, fd);
+    OW = cv_natural_out(W, fw, S, P, D, fd);
+    TORCH_CHECK(OH >= 1 && OW >= 1, op,
+                ": the dilated filter does not fit the padded input");
   }
+  cv_check_out(op, N, Cout, OH, OW, S);
+  cv_check_weight(op, "wk", wk, x, Cout, taps * Cin);
   auto y = at::empty({N, Cout, OH, OW},
                      x.options().dtype(out_f32 ? at::kFloat : at::kBFloat16),
                      at::MemoryFormat::ChannelsLast);
@@ -1165,8 +1268,6 @@ static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
   const ConvTilePlan plan = conv3x3_tile_plan(N, H, W, Cin, Cout, fh, fw, S, P,
                                               D, OH, OW, fd, out_f32, !stats);
   if (stats && D == 1 && !out_f32) {
-    TORCH_CHECK(x.is_cuda() && wk.device() == x.device(),
-                "conv_mfma_stats: x and wk must be on one GPU");
     const long M = (long)N * OH * OW;
     auto part = at::empty({(M + 255) / 256, 2, Cout},
                           x.options().dtype(at::kFloat));
@@ -1177,8 +1278,6 @@ static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
     return {y, part};
   }
   if (plan.halo) {
-    TORCH_CHECK(x.is_cuda() && wk.device() == x.device(),
-                "conv_mfma: x and wk must be on one GPU");
     tfosr_conv3x3_halo(x.data_ptr(), wk.contiguous().data_ptr(), y.data_ptr(),
                        plan.bm, N, H, W, Cin, (int)Cout, cur_stream());
     return {y, c10::nullopt};
@@ -1187,6 +1286,260 @@ static std::pair<at::Tensor, c10::optional<at::Tensor>> conv_mfma_impl(
                   y.data_ptr(), /*out_bf16=*/out_f32 ? 0 : 1, N, H, W, Cin,
                   Cout, OH, OW, S, P, taps, fw, D, 0, (int)fd, cur_stream());
   return {y, c10::nullopt};
+}
+
+// Generalized implicit-GEMM conv: taps in {1,9}, stride S, pad P, input
+// dilation D (the stored input is read as if zero-dilated by D). OH/OW are
+// explicit because backward-data output size is not derivable from the
+// stored input dims. One kernel covers conv1x1/conv3x3 fwd at stride 1/2,
+// their backward-data, and ConvTranspose2d k3 s2 (survey §2.3 rows 1-2).
+//
+// fd is the FILTER dilation (atrous conv): tap (r, s) reads the input at
+// offset (r*fd, s*fd), so the natural output size is
+// (H + 2P - fd*(fh-1) - 1)/S + 1. out_f32 returns the fp32 accumulator
+// unrounded instead of bf16.
+static at::Tensor conv_mfma(at::Tensor x, at::Tensor wk, long Cout, long fh,
+                            long fw, long S, long P, long D, long OH, long OW,
+                            long fd, bool out_f32) {
+  return conv_mfma_impl(x, wk, Cout, fh, fw, S, P, D, OH, OW, fd, out_f32,
+                        /*stats=*/false).first;
+}
+
+// -> (y, part, rows_per_tile): y is conv_mfma(...) bit for bit; part holds
+// y's per-tile BatchNorm partials for bn_fwd_train_pre, or None
+// (rows_per_tile 0) where the launch has no statistics epilogue (input
+// dilation 2 or fp32 output) and the caller keeps the separate pass.
+static py::tuple conv_mfma_stats(at::Tensor x, at::Tensor wk, long Cout,
+                                 long fh, long fw, long S, long P, long D,
+                                 long OH, long OW, long fd, bool out_f32) {
+  auto r = conv_mfma_impl(x, wk, Cout, fh, fw, S, P, D, OH, OW, fd, out_f32,
+                          /*stats=*/true);
+  if (!r.second.has_value()) return py::make_tuple(r.first, py::none(), 0);
+  return py::make_tuple(r.first, *r.second, 256);
+}
+
+// Host only: the kernel conv_mfma would launch for this call under the
+// current TFOS_CONV3X3_TILE, with its tile, tile count and grid, and the
+// largest W the halo kernel can stage (OH/OW < 0: the natural size).
+static py::dict conv3x3_halo_plan(long N, long H, long W, long Cin, long Cout,
+                                  long fh, long fw, long S, long P, long D,
+                                  long OH, long OW, long fd, bool out_f32) {
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && S > 0 &&
+              fd > 0 && D > 0, "conv3x3_halo_plan: bad dims");
+  if (OH < 0) {
+    OH = cv_natural_out(H, fh, S, P, D, fd);
+    OW = cv_natural_out(W, fw, S, P, D, fd);
+  }
+  const ConvTilePlan p = conv3x3_tile_plan(N, H, W, Cin, Cout, fh, fw, S, P,
+                                           D, OH, OW, fd, out_f32, true);
+  py::dict d;
+  d["kernel"] = p.halo ? "halo" : "im2col";
+  d["BM"] = p.bm;
+  d["BN"] = p.bn;
+  d["tiles"] = p.tiles;
+  d["grid"] = p.grid;
+  d["max_w"] = p.max_w;
+  return d;
+}
+
+// conv_mfma accumulating INTO an existing channels_last tensor:
+// out += conv(x, wk) — fuses the residual-join gradient accumulation the
+// eager autograd would do as a separate whole-tensor add (8.4 ms/step of
+// CUDAFunctor_add at ResNet-50 b1024, profiles/README r01).
+static at::Tensor conv_mfma_acc(at::Tensor x, at::Tensor wk, at::Tensor out,
+                                long fh, long fw, long S, long P, long D) {
+  const char* op = "conv_mfma_acc";
+  cv_check_act(op, "x", x, 32);
+  cv_check_act(op, "out", out, 1);
+  cv_check_device(op, "out", out, x);
+  cv_check_filter(op, fh, fw, S, P, D, /*fd=*/1);
+  int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  long taps = fh * fw;
+  long Cout = out.size(1), OH = out.size(2), OW = out.size(3);
+  TORCH_CHECK(out.size(0) == N, op, ": out must have x's batch ", N, ", got ",
+              out.size(0));
+  cv_check_out(op, N, Cout, OH, OW, S);
+  cv_check_weight(op, "wk", wk, x, Cout, taps * Cin);
+  const void* guard = zero_guard(x);
+  tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard,
+                  out.data_ptr(), /*out_bf16=*/1, N, H, W, Cin, Cout, OH, OW,
+                  S, P, taps, fw, D, 1, /*fd=*/1, cur_stream());
+  return out;
+}
+
+// One parity class of a stride-2 backward-data / transposed conv:
+// out[oh*2+oh0, ow*2+ow0] = conv(x, wk_class) with the class's taps
+// (list of (r,s) pairs). wk_class: [Cout, ntaps*Cin]. Writes into `out`
+// (pre-allocated [N, Cout, OHr, OWr] channels_last; classes disjoint).
+static at::Tensor conv_par(at::Tensor x, at::Tensor wk, at::Tensor out,
+                           std::vector<long> taps_r, std::vector<long> taps_s,
+                           long P, bool accum) {
+  const char* op = "conv_par";
+  cv_check_act(op, "x", x, 32);
+  cv_check_act(op, "out", out, 1);
+  cv_check_device(op, "out", out, x);
+  int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(out.size(0) == N, op, ": out must have x's batch ", N, ", got ",
+              out.size(0));
+  long ntaps = (long)taps_r.size();
+  TORCH_CHECK(ntaps >= 1 && ntaps <= 8 && taps_s.size() == (size_t)ntaps, op,
+              ": taps_r and taps_s must be equally long lists of 1 to 8 "
+              "taps, got ", taps_r.size(), " and ", taps_s.size());
+  TORCH_CHECK(P >= 0 && P <= kMaxTapReach, op, ": padding must be in [0, ",
+              kMaxTapReach, "], got ", P);
+  // the output parity (oh0, ow0) of the class follows from any of its taps:
+  // ihv = (oh*2+oh0) - P + r must be even, so every tap has one parity; a
+  // tap is packed into four bits each of r and s
+  for (long i = 0; i < ntaps; ++i) {
+    TORCH_CHECK(taps_r[i] >= 0 && taps_r[i] <= 15 && taps_s[i] >= 0 &&
+                    taps_s[i] <= 15,
+                op, ": tap (", taps_r[i], ", ", taps_s[i],
+                ") is outside [0, 15]");
+    TORCH_CHECK(taps_r[i] % 2 == taps_r[0] % 2 &&
+                    taps_s[i] % 2 == taps_s[0] % 2,
+                op, ": tap (", taps_r[i], ", ", taps_s[i],
+                ") is not in the parity class of tap (", taps_r[0], ", ",
+                taps_s[0], ")");
+  }
+  long Cout = out.size(1), OHr = out.size(2), OWr = out.size(3);
+  cv_check_weight(op, "wk", wk, x, Cout, ntaps * Cin);
+  long oh0 = ((P - taps_r[0]) % 2 + 2) % 2;
+  long ow0 = ((P - taps_s[0]) % 2 + 2) % 2;
+  long OHs = (OHr - oh0 + 1) / 2, OWs = (OWr - ow0 + 1) / 2;
+  if (OHs <= 0 || OWs <= 0) return out;
+  cv_check_out(op, N, Cout, OHs, OWs, /*S=*/2);
+  unsigned long pack = 0;
+  for (long i = 0; i < ntaps; ++i)
+    pack |= ((unsigned long)((taps_r[i] << 4) | taps_s[i])) << (i * 8);
+  const void* guard = zero_guard(x);
+  tfosr_conv_par(x.data_ptr(), wk.contiguous().data_ptr(), guard,
+                 out.data_ptr(), N, H, W, Cin, (int)Cout, (int)OHs,
+                 (int)OWs, (int)P, (int)ntaps, pack, (int)oh0, (int)ow0,
+                 (int)OWr, OHr * OWr, accum ? 1 : 0, cur_stream());
+  return out;
+}
+
+// ResNet stem: 7x7/s2/p3 conv over a pre-padded NHWC4 image
+// ([N,4,230,230] channels_last bf16, Cin 3->4 zero-padded, spatial pad 3
+// baked in); weight pre-packed to [Cout, 7*32] with zero columns for the
+// pads. Output [N, Cout, 112, 112].
+static at::Tensor conv_stem(at::Tensor x4, at::Tensor w224, long Cout) {
+  const char* op = "conv_stem";
+  cv_check_act(op, "x4", x4, 4, /*exact=*/true);
+  int N = x4.size(0), Hp = x4.size(2), Wp = x4.size(3);
+  TORCH_CHECK(Hp >= 7 && Wp >= 7, op, ": the padded image must be at least "
+              "7x7, got ", Hp, "x", Wp);
+  int OH = cv_natural_out(Hp, 7, 2, 0, 1, 1);
+  int OW = cv_natural_out(Wp, 7, 2, 0, 1, 1);
+  cv_check_out(op, N, Cout, OH, OW, /*S=*/2);
+  cv_check_weight(op, "w224", w224, x4, Cout, 224);
+  auto y = at::empty({N, Cout, OH, OW}, x4.options(),
+                     at::MemoryFormat::ChannelsLast);
+  const void* guard = zero_guard(x4);
+  tfosr_conv_stem(x4.data_ptr(), w224.contiguous().data_ptr(),
+                  guard, y.data_ptr(), N, Hp, Wp, Cout, OH, OW,
+                  cur_stream());
+  return y;
+}
+
+// The weight-gradient entries take dy of the forward's natural output size
+// for x and the given filter, with x's batch; M = N*OH*OW <= INT_MAX.
+static void cv_check_wrw_pair(const char* op, const at::Tensor& dy,
+                              const at::Tensor& x, long xc, bool x_exact,
+                              long R, long S_f, long stride, long P,
+                              long fd) {
+  cv_check_act(op, "dy", dy, 8);
+  cv_check_act(op, "x", x, xc, x_exact);
+  cv_check_device(op, "x", x, dy);
+  cv_check_filter(op, R, S_f, stride, P, /*D=*/1, fd);
+  const long N = x.size(0);
+  const long OH = cv_natural_out(x.size(2), R, stride, P, 1, fd);
+  const long OW = cv_natural_out(x.size(3), S_f, stride, P, 1, fd);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == OH && dy.size(3) == OW, op,
+              ": x ", x.sizes(), " with a ", R, "x", S_f, " filter, stride ",
+              stride, ", padding ", P, ", dilation ", fd,
+              " gives a gradient of [", N, ", Cout, ", OH, ", ", OW,
+              "], got ", dy.sizes());
+  TORCH_CHECK(OH <= INT_MAX / OW && N <= INT_MAX / (OH * OW), op, ": ", N,
+              "x", OH, "x", OW, " gradient pixels exceed the kernels' 32-bit "
+              "pixel index");
+}
+
+// wrw v2: MFMA + hardware transpose-reads + split-M workspace.
+// dy [N,Cout,OH,OW] cl, x [N,Cin,H,W] cl; filter R x S_f, conv stride,
+// pad P. Returns fp32 dW [Cout, R*S_f*Cin].
+// fd: filter dilation of the 3x3 case (dW tap (r, s) pairs dy[oh, ow]
+// with x[oh*stride - P + r*fd, ow*stride - P + s*fd]).
+static at::Tensor conv_wrw2(at::Tensor dy, at::Tensor x, long R, long S_f,
+                            long stride, long P, long fd) {
+  const char* op = "conv_wrw2";
+  long taps = R * S_f;
+  TORCH_CHECK(taps == 1 || taps == 9, op, " supports 1x1 and 3x3, got ", R,
+              "x", S_f);
+  TORCH_CHECK(fd >= 1, op, ": filter dilation fd must be >= 1, got ", fd);
+  TORCH_CHECK(taps != 1 || fd == 1, op,
+              ": a 1x1 filter has no dilation, fd must be 1");
+  // the 1x1 kernel reads x at (oh*stride, ow*stride) with no padding test
+  TORCH_CHECK(taps != 1 || P == 0, op,
+              ": a 1x1 filter takes no padding, P must be 0, got ", P);
+  cv_check_wrw_pair(op, dy, x, 8, false, R, S_f, stride, P, fd);
+  int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  int Cout = dy.size(1), OH = dy.size(2), OW = dy.size(3);
+  long M = (long)N * OH * OW;
+  int split = tfosr_wrw2_split(Cout, Cin, M);
+  long K = taps * (long)Cin;
+  // the split reduce indexes the workspace with 32-bit offsets
+  TORCH_CHECK((long)split * Cout * K < (1L << 32), op,
+              ": the split workspace exceeds 2^32 elements");
+  auto ws = at::empty({(long)split, (long)Cout * K},
+                      x.options().dtype(at::kFloat));
+  auto dW = at::empty({(long)Cout, K}, x.options().dtype(at::kFloat));
+  const void* guard = zero_guard(x);
+  tfosr_conv_wrw2(dy.data_ptr(), x.data_ptr(), guard,
+                  ws.data_ptr<float>(), dW.data_ptr<float>(), N, H, W, Cin,
+                  Cout, OH, OW, R, S_f, stride, P, split, (int)fd,
+                  cur_stream());
+  return dW;
+}
+
+// stem weight gradient over the same NHWC4 padded view: returns fp32
+// [Cout, 7*32] (rows x (8 px x 4 ch), pads included — caller unpacks)
+static at::Tensor conv_stem_wrw(at::Tensor dy, at::Tensor x4) {
+  const char* op = "conv_stem_wrw";
+  // the geometry is the 7x7 filter's; the kernel sees its rows as 7 taps
+  cv_check_wrw_pair(op, dy, x4, 4, true, /*R=*/7, /*S_f=*/7, /*stride=*/2,
+                    /*P=*/0, /*fd=*/1);
+  int N = x4.size(0), Hp = x4.size(2), Wp = x4.size(3);
+  int Cout = dy.size(1), OH = dy.size(2), OW = dy.size(3);
+  long M = (long)N * OH * OW;
+  int split = tfosr_wrw2_split(Cout, 32, M);
+  long K = 7L * 32;
+  TORCH_CHECK((long)split * Cout * K < (1L << 32), op,
+              ": the split workspace exceeds 2^32 elements");
+  auto ws = at::empty({(long)split, (long)Cout * K},
+                      x4.options().dtype(at::kFloat));
+  auto dW = at::empty({(long)Cout, K}, x4.options().dtype(at::kFloat));
+  const void* guard = zero_guard(x4);
+  tfosr_conv_wrw2(dy.data_ptr(), x4.data_ptr(), guard,
+                  ws.data_ptr<float>(), dW.data_ptr<float>(), N, Hp, Wp,
+                  /*Cin=*/32, Cout, OH, OW, /*R=*/7, /*S_f=*/1,
+                  /*stride=*/2, /*P=*/0, split, /*fd=*/1, cur_stream());
+  return dW;
+}
+
+// The round-1 TN weight-gradient kernel (stride 1, undilated), kept as the
+// TFOS_WRW=mfma backend. Returns fp32 dW [Cout, R*S*Cin].
+static at::Tensor conv_wrw(at::Tensor dy, at::Tensor x, long R, long S,
+                           long P) {
+  cv_check_wrw_pair("conv_wrw", dy, x, 8, false, R, S, /*stride=*/1, P,
+                    /*fd=*/1);
+  int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  int Cout = dy.size(1), OH = dy.size(2), OW = dy.size(3);
+  auto dW = at::zeros({Cout, R * S * (long)Cin},
+                      x.options().dtype(at::kFloat));
+  tfosr_conv_wrw(dy.data_ptr(), x.data_ptr(), dW.data_ptr<float>(), N, H, W,
+                 Cin, Cout, OH, OW, R, S, P, cur_stream());
+  return dW;
 }
 
 // ---------------------------------------------------------------------------
@@ -1497,109 +1850,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                       K, S, P, cur_stream());
     return std::vector<at::Tensor>{y, idx};
   });
-  m.def("conv3x3_fwd", [](at::Tensor x, at::Tensor w9, long Cout, long S,
-                          long P) {
-    TORCH_CHECK(x.dim() == 4 && x.is_contiguous(at::MemoryFormat::ChannelsLast),
-                "conv3x3_fwd expects channels_last input");
-    TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-                w9.scalar_type() == at::kBFloat16);
-    int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-    TORCH_CHECK(Cin % 32 == 0, "conv3x3 requires Cin % 32 == 0");
-    TORCH_CHECK(w9.size(1) == 9 * Cin);
-    int OH = (H + 2 * P - 3) / S + 1, OW = (W + 2 * P - 3) / S + 1;
-    auto y = at::empty({N, Cout, OH, OW}, x.options(),
-                       at::MemoryFormat::ChannelsLast);
-    const void* guard = zero_guard(x);
-    tfosr_conv3x3(x.data_ptr(), w9.contiguous().data_ptr(), guard,
-                  y.data_ptr(), /*out_bf16=*/1, N, H, W, Cin, Cout, OH, OW,
-                  S, P, cur_stream());
-    return y;
-  });
-  // Generalized implicit-GEMM conv: taps in {1,9}, stride S, pad P, input
-  // dilation D (the stored input is read as if zero-dilated by D). OH/OW are
-  // explicit because backward-data output size is not derivable from the
-  // stored input dims. One kernel covers conv1x1/conv3x3 fwd at stride 1/2,
-  // their backward-data, and ConvTranspose2d k3 s2 (survey §2.3 rows 1-2).
-  //
-  // fd is the FILTER dilation (atrous conv): tap (r, s) reads the input at
-  // offset (r*fd, s*fd), so the natural output size is
-  // (H + 2P - fd*(fh-1) - 1)/S + 1. out_f32 returns the fp32 accumulator
-  // unrounded instead of bf16.
-  m.def("conv_mfma", [](at::Tensor x, at::Tensor wk, long Cout, long fh,
-                        long fw, long S, long P, long D, long OH, long OW,
-                        long fd, bool out_f32) {
-    return conv_mfma_impl(x, wk, Cout, fh, fw, S, P, D, OH, OW, fd, out_f32,
-                          /*stats=*/false).first;
-  }, py::arg("x"), py::arg("wk"), py::arg("Cout"), py::arg("fh"),
-     py::arg("fw"), py::arg("S"), py::arg("P"), py::arg("D"), py::arg("OH"),
-     py::arg("OW"), py::arg("fd") = 1, py::arg("out_f32") = false);
-  // Host only: the kernel conv_mfma would launch for this call under the
-  // current TFOS_CONV3X3_TILE, with its tile, tile count and grid, and the
-  // largest W the halo kernel can stage (OH/OW < 0: the natural size).
-  m.def("conv3x3_halo_plan", [](long N, long H, long W, long Cin, long Cout,
-                                long fh, long fw, long S, long P, long D,
-                                long OH, long OW, long fd, bool out_f32) {
-    TORCH_CHECK(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && S > 0 &&
-                fd > 0 && D > 0, "conv3x3_halo_plan: bad dims");
-    if (OH < 0) {
-      OH = ((H - 1) * D + 1 + 2 * P - fd * (fh - 1) - 1) / S + 1;
-      OW = ((W - 1) * D + 1 + 2 * P - fd * (fw - 1) - 1) / S + 1;
-    }
-    const ConvTilePlan p = conv3x3_tile_plan(N, H, W, Cin, Cout, fh, fw, S, P,
-                                             D, OH, OW, fd, out_f32, true);
-    py::dict d;
-    d["kernel"] = p.halo ? "halo" : "im2col";
-    d["BM"] = p.bm;
-    d["BN"] = p.bn;
-    d["tiles"] = p.tiles;
-    d["grid"] = p.grid;
-    d["max_w"] = p.max_w;
-    return d;
-  }, py::arg("N"), py::arg("H"), py::arg("W"), py::arg("Cin"),
-     py::arg("Cout"), py::arg("fh") = 3, py::arg("fw") = 3, py::arg("S") = 1,
-     py::arg("P") = 1, py::arg("D") = 1, py::arg("OH") = -1,
-     py::arg("OW") = -1, py::arg("fd") = 1, py::arg("out_f32") = false);
-  // -> (y, part, rows_per_tile): y is conv_mfma(...) bit for bit; part holds
-  // y's per-tile BatchNorm partials for bn_fwd_train_pre, or None
-  // (rows_per_tile 0) where the launch has no statistics epilogue (input
-  // dilation 2 or fp32 output) and the caller keeps the separate pass.
-  m.def("conv_mfma_stats", [](at::Tensor x, at::Tensor wk, long Cout, long fh,
-                              long fw, long S, long P, long D, long OH,
-                              long OW, long fd, bool out_f32) {
-    auto r = conv_mfma_impl(x, wk, Cout, fh, fw, S, P, D, OH, OW, fd, out_f32,
-                            /*stats=*/true);
-    if (!r.second.has_value()) return py::make_tuple(r.first, py::none(), 0);
-    return py::make_tuple(r.first, *r.second, 256);
-  }, py::arg("x"), py::arg("wk"), py::arg("Cout"), py::arg("fh"),
-     py::arg("fw"), py::arg("S"), py::arg("P"), py::arg("D"), py::arg("OH"),
-     py::arg("OW"), py::arg("fd") = 1, py::arg("out_f32") = false);
+  m.def("conv_mfma", &conv_mfma, py::arg("x"), py::arg("wk"), py::arg("Cout"),
+        py::arg("fh"), py::arg("fw"), py::arg("S"), py::arg("P"), py::arg("D"),
+        py::arg("OH"), py::arg("OW"), py::arg("fd") = 1,
+        py::arg("out_f32") = false);
+  m.def("conv3x3_halo_plan", &conv3x3_halo_plan, py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("Cin"), py::arg("Cout"), py::arg("fh") = 3,
+        py::arg("fw") = 3, py::arg("S") = 1, py::arg("P") = 1,
+        py::arg("D") = 1, py::arg("OH") = -1, py::arg("OW") = -1,
+        py::arg("fd") = 1, py::arg("out_f32") = false);
+  m.def("conv_mfma_stats", &conv_mfma_stats, py::arg("x"), py::arg("wk"),
+        py::arg("Cout"), py::arg("fh"), py::arg("fw"), py::arg("S"),
+        py::arg("P"), py::arg("D"), py::arg("OH"), py::arg("OW"),
+        py::arg("fd") = 1, py::arg("out_f32") = false);
   m.def("gemm_bt_stats", &gemm_bt_stats, py::arg("a"), py::arg("b"));
   m.def("bn_fwd_train_pre", &bn_fwd_train_pre);
   m.def("bn_dual_fwd_train_pre", &bn_dual_fwd_train_pre);
   m.def("bn_batch_stats", &bn_batch_stats);
-  // conv_mfma accumulating INTO an existing channels_last tensor:
-  // out += conv(x, wk) — fuses the residual-join gradient accumulation the
-  // eager autograd would do as a separate whole-tensor add (8.4 ms/step of
-  // CUDAFunctor_add at ResNet-50 b1024, profiles/README r01).
-  m.def("conv_mfma_acc", [](at::Tensor x, at::Tensor wk, at::Tensor out,
-                            long fh, long fw, long S, long P, long D) {
-    TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                out.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-                wk.scalar_type() == at::kBFloat16 &&
-                out.scalar_type() == at::kBFloat16);
-    int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-    TORCH_CHECK(Cin % 32 == 0, "conv_mfma requires Cin % 32 == 0");
-    long taps = fh * fw;
-    TORCH_CHECK(wk.size(1) == taps * Cin);
-    long Cout = out.size(1), OH = out.size(2), OW = out.size(3);
-    TORCH_CHECK(out.size(0) == N);
-    const void* guard = zero_guard(x);
-    tfosr_conv_mfma(x.data_ptr(), wk.contiguous().data_ptr(), guard,
-                    out.data_ptr(), /*out_bf16=*/1, N, H, W, Cin, Cout, OH, OW,
-                    S, P, taps, fw, D, 1, /*fd=*/1, cur_stream());
-    return out;
-  });
+  m.def("conv_mfma_acc", &conv_mfma_acc, py::arg("x"), py::arg("wk"),
+        py::arg("out"), py::arg("fh"), py::arg("fw"), py::arg("S"),
+        py::arg("P"), py::arg("D"));
   // gemm accumulating into an existing [M, N] tensor: C += A @ B^T.
   // bf16 only: the launcher instantiates the accumulating epilogue for bf16
   // output alone, so an fp32 c would be overwritten instead of added to.
@@ -1623,52 +1893,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                       /*out_bf16=*/1, M, Nn, K, 1, cur_stream());
     return c;
   });
-  // wrw v2: MFMA + hardware transpose-reads + split-M workspace.
-  // dy [N,Cout,OH,OW] cl, x [N,Cin,H,W] cl; filter R x S_f, conv stride,
-  // pad P. Returns fp32 dW [Cout, R*S_f*Cin].
-  // fd: filter dilation of the 3x3 case (dW tap (r, s) pairs dy[oh, ow]
-  // with x[oh*stride - P + r*fd, ow*stride - P + s*fd]).
-  m.def("conv_wrw2", [](at::Tensor dy, at::Tensor x, long R, long S_f,
-                        long stride, long P, long fd) {
-    TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                x.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 &&
-                x.scalar_type() == at::kBFloat16);
-    int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-    int Cout = dy.size(1), OH = dy.size(2), OW = dy.size(3);
-    TORCH_CHECK(Cin % 8 == 0 && Cout % 8 == 0,
-                "conv_wrw2 needs channel counts % 8 == 0");
-    long taps = R * S_f;
-    TORCH_CHECK(taps == 1 || taps == 9, "conv_wrw2 supports 1x1 and 3x3");
-    TORCH_CHECK(fd >= 1, "conv_wrw2: filter dilation fd must be >= 1, got ",
-                fd);
-    TORCH_CHECK(taps != 1 || fd == 1,
-                "conv_wrw2: a 1x1 filter has no dilation, fd must be 1");
-    TORCH_CHECK(fd <= kMaxTapReach && fd * (R - 1) <= kMaxTapReach &&
-                    fd * (S_f - 1) <= kMaxTapReach,
-                "conv_wrw2: fd, fd*(R-1) and fd*(S_f-1) must be <= ",
-                kMaxTapReach);
-    long M = (long)N * OH * OW;
-    int split = tfosr_wrw2_split(Cout, Cin, M);
-    long K = taps * (long)Cin;
-    // the split reduce indexes the workspace with 32-bit offsets
-    TORCH_CHECK((long)split * Cout * K < (1L << 32),
-                "conv_wrw2: the split workspace exceeds 2^32 elements");
-    auto ws = at::empty({(long)split, (long)Cout * K},
-                        x.options().dtype(at::kFloat));
-    auto dW = at::empty({(long)Cout, K}, x.options().dtype(at::kFloat));
-    const void* guard = zero_guard(x);
-    tfosr_conv_wrw2(dy.data_ptr(), x.data_ptr(), guard,
-                    ws.data_ptr<float>(), dW.data_ptr<float>(), N, H, W, Cin,
-                    Cout, OH, OW, R, S_f, stride, P, split, (int)fd,
-                    cur_stream());
-    return dW;
-  }, py::arg("dy"), py::arg("x"), py::arg("R"), py::arg("S_f"),
-     py::arg("stride"), py::arg("P"), py::arg("fd") = 1);
-  // One parity class of a stride-2 backward-data / transposed conv:
-  // out[oh*2+oh0, ow*2+ow0] = conv(x, wk_class) with the class's taps
-  // (list of (r,s) pairs). wk_class: [Cout, ntaps*Cin]. Writes into `out`
-  // (pre-allocated [N, Cout, OHr, OWr] channels_last; classes disjoint).
+  m.def("conv_wrw2", &conv_wrw2, py::arg("dy"), py::arg("x"), py::arg("R"),
+        py::arg("S_f"), py::arg("stride"), py::arg("P"), py::arg("fd") = 1);
   // batched weight pack: desc buffer layout must match PackDesc in
   // elementwise.hip (built by ops/packplan.py); one launch packs every
   // per-step weight transform into the bf16 arena
@@ -1696,94 +1922,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     tfosr_pack_bf16(descs.data_ptr(), cum.data_ptr(), (int)ndesc,
                     arena.data_ptr(), total, cur_stream());
   });
-  m.def("conv_par", [](at::Tensor x, at::Tensor wk, at::Tensor out,
-                       std::vector<long> taps_r, std::vector<long> taps_s,
-                       long P, bool accum) {
-    TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                out.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
-                wk.scalar_type() == at::kBFloat16 &&
-                out.scalar_type() == at::kBFloat16);
-    int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-    TORCH_CHECK(Cin % 32 == 0);
-    long ntaps = (long)taps_r.size();
-    TORCH_CHECK(ntaps >= 1 && ntaps <= 8 && taps_s.size() == (size_t)ntaps);
-    TORCH_CHECK(wk.size(1) == ntaps * Cin);
-    long Cout = out.size(1), OHr = out.size(2), OWr = out.size(3);
-    // parity offsets come from the tap list: ihv = (oh*2+oh0) - P + r must be
-    // even for every class tap — caller passes oh0/ow0 via taps parity
-    // (we derive them from the first tap)
-    long oh0 = ((P - taps_r[0]) % 2 + 2) % 2;
-    long ow0 = ((P - taps_s[0]) % 2 + 2) % 2;
-    long OHs = (OHr - oh0 + 1) / 2, OWs = (OWr - ow0 + 1) / 2;
-    if (OHs <= 0 || OWs <= 0) return out;
-    unsigned long pack = 0;
-    for (long i = 0; i < ntaps; ++i)
-      pack |= ((unsigned long)((taps_r[i] << 4) | taps_s[i])) << (i * 8);
-    const void* guard = zero_guard(x);
-    tfosr_conv_par(x.data_ptr(), wk.contiguous().data_ptr(), guard,
-                   out.data_ptr(), N, H, W, Cin, (int)Cout, (int)OHs,
-                   (int)OWs, (int)P, (int)ntaps, pack, (int)oh0, (int)ow0,
-                   (int)OWr, OHr * OWr, accum ? 1 : 0, cur_stream());
-    return out;
-  });
-  // ResNet stem: 7x7/s2/p3 conv over a pre-padded NHWC4 image
-  // ([N,4,230,230] channels_last bf16, Cin 3->4 zero-padded, spatial pad 3
-  // baked in); weight pre-packed to [Cout, 7*32] with zero columns for the
-  // pads. Output [N, Cout, 112, 112].
-  m.def("conv_stem", [](at::Tensor x4, at::Tensor w224, long Cout) {
-    TORCH_CHECK(x4.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                x4.size(1) == 4, "conv_stem expects NHWC4 padded input");
-    TORCH_CHECK(x4.scalar_type() == at::kBFloat16 &&
-                w224.scalar_type() == at::kBFloat16);
-    TORCH_CHECK(w224.size(1) == 224);
-    int N = x4.size(0), Hp = x4.size(2), Wp = x4.size(3);
-    int OH = (Hp - 7) / 2 + 1, OW = (Wp - 7) / 2 + 1;
-    auto y = at::empty({N, Cout, OH, OW}, x4.options(),
-                       at::MemoryFormat::ChannelsLast);
-    const void* guard = zero_guard(x4);
-    tfosr_conv_stem(x4.data_ptr(), w224.contiguous().data_ptr(),
-                    guard, y.data_ptr(), N, Hp, Wp, Cout, OH, OW,
-                    cur_stream());
-    return y;
-  });
-  // stem weight gradient over the same NHWC4 padded view: returns fp32
-  // [Cout, 7*32] (rows x (8 px x 4 ch), pads included — caller unpacks)
-  m.def("conv_stem_wrw", [](at::Tensor dy, at::Tensor x4) {
-    TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                x4.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 &&
-                x4.scalar_type() == at::kBFloat16 && x4.size(1) == 4);
-    int N = x4.size(0), Hp = x4.size(2), Wp = x4.size(3);
-    int Cout = dy.size(1), OH = dy.size(2), OW = dy.size(3);
-    long M = (long)N * OH * OW;
-    int split = tfosr_wrw2_split(Cout, 32, M);
-    long K = 7L * 32;
-    TORCH_CHECK((long)split * Cout * K < (1L << 32),
-                "conv_stem_wrw: the split workspace exceeds 2^32 elements");
-    auto ws = at::empty({(long)split, (long)Cout * K},
-                        x4.options().dtype(at::kFloat));
-    auto dW = at::empty({(long)Cout, K}, x4.options().dtype(at::kFloat));
-    const void* guard = zero_guard(x4);
-    tfosr_conv_wrw2(dy.data_ptr(), x4.data_ptr(), guard,
-                    ws.data_ptr<float>(), dW.data_ptr<float>(), N, Hp, Wp,
-                    /*Cin=*/32, Cout, OH, OW, /*R=*/7, /*S_f=*/1,
-                    /*stride=*/2, /*P=*/0, split, /*fd=*/1, cur_stream());
-    return dW;
-  });
-  m.def("conv_wrw", [](at::Tensor dy, at::Tensor x, long R, long S, long P) {
-    TORCH_CHECK(dy.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                x.is_contiguous(at::MemoryFormat::ChannelsLast));
-    TORCH_CHECK(dy.scalar_type() == at::kBFloat16 &&
-                x.scalar_type() == at::kBFloat16);
-    int N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
-    int Cout = dy.size(1), OH = dy.size(2), OW = dy.size(3);
-    auto dW = at::zeros({Cout, R * S * (long)Cin},
-                        x.options().dtype(at::kFloat));
-    tfosr_conv_wrw(dy.data_ptr(), x.data_ptr(), dW.data_ptr<float>(), N, H, W,
-                   Cin, Cout, OH, OW, R, S, P, cur_stream());
-    return dW;
-  });
+  m.def("conv_par", &conv_par, py::arg("x"), py::arg("wk"), py::arg("out"),
+        py::arg("taps_r"), py::arg("taps_s"), py::arg("P"), py::arg("accum"));
+  m.def("conv_stem", &conv_stem, py::arg("x4"), py::arg("w224"),
+        py::arg("Cout"));
+  m.def("conv_stem_wrw", &conv_stem_wrw, py::arg("dy"), py::arg("x4"));
+  m.def("conv_wrw", &conv_wrw, py::arg("dy"), py::arg("x"), py::arg("R"),
+        py::arg("S"), py::arg("P"));
   m.def("maxpool_bwd", [](at::Tensor dy, at::Tensor idx, long H, long W,
                           long K, long S, long P) {
     TORCH_CHECK(dy.dim() == 4, "maxpool_bwd expects a 4-D gradient");

@@ -269,58 +269,49 @@ __global__ __launch_bounds__(512, 1) void conv3x3_kernel(
   }
 }
 
-// part != nullptr (bf16 output, D == 1, no ACC): the STATS kernels, which also
-// fill part[ceil(M / 256)][2][Cout]
-template <int D, bool ACC, bool STATS = false>
-static void launch_conv(const void* X, const void* W9, const void* guard,
-                        void* Y, int out_bf16, int N, int H, int W, int Cin,
-                        int Cout, int OH, int OW, int S, int P, int taps,
-                        int fw, int pixst, int fd, hipStream_t s,
-                        float* part = nullptr) {
-  const long M = (long)N * OH * OW;
-  if (Cout >= 192) {
-    int ntm = (int)((M + 255) / 256), ntn = (Cout + 255) / 256;
-    dim3 grid(ntm * ntn);
-    if (out_bf16)
-      hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 2, 4, 8, D, ACC, false, STATS>),
-                         grid,
-                         dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
-                         (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
-                         OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
-                         fd, part);
-    else
-      hipLaunchKernelGGL((conv3x3_kernel<float, 2, 4, 8, D, ACC>), grid,
-                         dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
-                         (const bf16_t*)guard, (float*)Y, N, H, W, Cin, Cout,
-                         OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
-                         fd, (float*)nullptr);
-    return;
-  }
-  int ntm = (int)((M + 255) / 256), ntn = (Cout + 127) / 128;
-  dim3 grid(ntm * ntn);
-  if (out_bf16)
-    hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 4, 2, 4, D, ACC, false, STATS>),
-                       grid,
-                       dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
-                       (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
-                       OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
-                         fd, part);
+// What one launch of conv3x3_kernel is given. OH x OW is the grid's pixel
+// space: the output itself, or under PAR one parity class of the real output
+// [.., OHOWr / OWr, OWr], whose taps are tap_pack and whose first pixel is
+// (oh0, ow0). Without PAR the kernel never reads those four.
+struct ConvLaunch {
+  const void *X, *W9, *guard;
+  void* Y;
+  int N, H, W, Cin, Cout, OH, OW, S, P, taps, fw, pixst, fd;
+  unsigned long tap_pack = 0;
+  int oh0 = 0, ow0 = 0, OWr = 0;
+  long OHOWr = 0;
+  float* part = nullptr;  // STATS: [ceil(N*OH*OW / 256)][2][Cout]
+};
+
+// The one place a tile is picked and a conv3x3_kernel launched: 256x256 for
+// Cout >= 192, else 256x128 (both 256 rows, 512 threads).
+template <typename OT, int D, bool ACC, bool PAR, bool STATS>
+static void launch_tile(const ConvLaunch& a, hipStream_t s) {
+  const long M = (long)a.N * a.OH * a.OW;
+  const int ntm = (int)((M + 255) / 256);
+  auto launch = [&](auto kernel, int bn) {
+    hipLaunchKernelGGL(kernel, dim3(ntm * ((a.Cout + bn - 1) / bn)), dim3(512),
+                       0, s, (const bf16_t*)a.X, (const bf16_t*)a.W9,
+                       (const bf16_t*)a.guard, (OT*)a.Y, a.N, a.H, a.W, a.Cin,
+                       a.Cout, a.OH, a.OW, a.S, a.P, a.taps, a.fw, a.pixst,
+                       a.tap_pack, a.oh0, a.ow0, PAR ? a.OWr : a.OW,
+                       PAR ? a.OHOWr : (long)a.OH * a.OW, a.fd, a.part);
+  };
+  if (a.Cout >= 192)
+    launch(conv3x3_kernel<OT, 2, 4, 8, D, ACC, PAR, STATS>, 256);
   else
-    hipLaunchKernelGGL((conv3x3_kernel<float, 4, 2, 4, D, ACC>), grid,
-                       dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)W9,
-                       (const bf16_t*)guard, (float*)Y, N, H, W, Cin, Cout,
-                       OH, OW, S, P, taps, fw, pixst, 0UL, 0, 0, OW, (long)OH * OW,
-                         fd, (float*)nullptr);
+    launch(conv3x3_kernel<OT, 4, 2, 4, D, ACC, PAR, STATS>, 128);
+}
+
+template <int D, bool ACC>
+static void launch_conv(const ConvLaunch& a, int out_bf16, hipStream_t s) {
+  if (out_bf16)
+    launch_tile<bf16_t, D, ACC, false, false>(a, s);
+  else
+    launch_tile<float, D, ACC, false, false>(a, s);
 }
 
 extern "C" {
-
-void tfosr_conv3x3(const void* X, const void* W9, const void* guard, void* Y,
-                   int out_bf16, int N, int H, int W, int Cin, int Cout,
-                   int OH, int OW, int S, int P, hipStream_t s) {
-  launch_conv<1, false>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH, OW,
-                        S, P, 9, 3, Cin, /*fd=*/1, s);
-}
 
 // General entry: taps = fh*fw; input dilation Dil in {1, 2}; filter dilation
 // fd >= 1 (tap (r, s) reads the input at offset (r*fd, s*fd)). fd > 1 is
@@ -330,20 +321,19 @@ void tfosr_conv_mfma(const void* X, const void* W9, const void* guard, void* Y,
                      int out_bf16, int N, int H, int W, int Cin, int Cout,
                      int OH, int OW, int S, int P, int taps, int fw, int Dil,
                      int accum, int fd, hipStream_t s) {
+  const bool plain = Dil != 2 && !accum;
+  const ConvLaunch a = {X, W9, guard, Y, N, H, W, Cin, Cout, OH, OW, S, P,
+                        taps, fw, /*pixst=*/Cin, plain ? fd : 1};
   if (Dil == 2) {
     if (accum)
-      launch_conv<2, true>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH,
-                           OW, S, P, taps, fw, Cin, 1, s);
+      launch_conv<2, true>(a, out_bf16, s);
     else
-      launch_conv<2, false>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH,
-                            OW, S, P, taps, fw, Cin, 1, s);
+      launch_conv<2, false>(a, out_bf16, s);
   } else {
     if (accum)
-      launch_conv<1, true>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH,
-                           OW, S, P, taps, fw, Cin, 1, s);
+      launch_conv<1, true>(a, out_bf16, s);
     else
-      launch_conv<1, false>(X, W9, guard, Y, out_bf16, N, H, W, Cin, Cout, OH,
-                            OW, S, P, taps, fw, Cin, fd, s);
+      launch_conv<1, false>(a, out_bf16, s);
   }
 }
 
@@ -354,8 +344,10 @@ void tfosr_conv_mfma_stats(const void* X, const void* W9, const void* guard,
                            void* Y, float* part, int N, int H, int W, int Cin,
                            int Cout, int OH, int OW, int S, int P, int taps,
                            int fw, int fd, hipStream_t s) {
-  launch_conv<1, false, true>(X, W9, guard, Y, /*out_bf16=*/1, N, H, W, Cin,
-                              Cout, OH, OW, S, P, taps, fw, Cin, fd, s, part);
+  ConvLaunch a = {X, W9, guard, Y, N, H, W, Cin, Cout, OH, OW, S, P, taps, fw,
+                  /*pixst=*/Cin, fd};
+  a.part = part;
+  launch_tile<bf16_t, 1, false, false, true>(a, s);
 }
 
 // Parity-decomposed stride-2 backward-data / transposed-conv class launch:
@@ -366,38 +358,13 @@ void tfosr_conv_par(const void* X, const void* Wk, const void* guard, void* Y,
                     int N, int H, int W, int Cin, int Cout, int OHs, int OWs,
                     int P, int ntaps, unsigned long tap_pack, int oh0, int ow0,
                     int OWr, long OHOWr, int accum, hipStream_t s) {
-  const long M = (long)N * OHs * OWs;
-  if (Cout >= 192) {
-    int ntm = (int)((M + 255) / 256), ntn = (Cout + 255) / 256;
-    dim3 grid(ntm * ntn);
-    if (accum)
-      hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 2, 4, 8, 2, true, true>),
-                         grid, dim3(512), 0, s, (const bf16_t*)X,
-                         (const bf16_t*)Wk, (const bf16_t*)guard, (bf16_t*)Y,
-                         N, H, W, Cin, Cout, OHs, OWs, 1, P, ntaps, 1, Cin,
-                         tap_pack, oh0, ow0, OWr, OHOWr, /*fd=*/1, (float*)nullptr);
-    else
-      hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 2, 4, 8, 2, false, true>),
-                         grid, dim3(512), 0, s, (const bf16_t*)X,
-                         (const bf16_t*)Wk, (const bf16_t*)guard, (bf16_t*)Y,
-                         N, H, W, Cin, Cout, OHs, OWs, 1, P, ntaps, 1, Cin,
-                         tap_pack, oh0, ow0, OWr, OHOWr, /*fd=*/1, (float*)nullptr);
-    return;
-  }
-  int ntm = (int)((M + 255) / 256), ntn = (Cout + 127) / 128;
-  dim3 grid(ntm * ntn);
+  const ConvLaunch a = {X, Wk, guard, Y, N, H, W, Cin, Cout, OHs, OWs, /*S=*/1,
+                        P, ntaps, /*fw=*/1, /*pixst=*/Cin, /*fd=*/1, tap_pack,
+                        oh0, ow0, OWr, OHOWr};
   if (accum)
-    hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 4, 2, 4, 2, true, true>), grid,
-                       dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)Wk,
-                       (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
-                       OHs, OWs, 1, P, ntaps, 1, Cin, tap_pack, oh0, ow0,
-                       OWr, OHOWr, /*fd=*/1, (float*)nullptr);
+    launch_tile<bf16_t, 2, true, true, false>(a, s);
   else
-    hipLaunchKernelGGL((conv3x3_kernel<bf16_t, 4, 2, 4, 2, false, true>), grid,
-                       dim3(512), 0, s, (const bf16_t*)X, (const bf16_t*)Wk,
-                       (const bf16_t*)guard, (bf16_t*)Y, N, H, W, Cin, Cout,
-                       OHs, OWs, 1, P, ntaps, 1, Cin, tap_pack, oh0, ow0,
-                       OWr, OHOWr, /*fd=*/1, (float*)nullptr);
+    launch_tile<bf16_t, 2, false, true, false>(a, s);
 }
 
 // ResNet stem 7x7/s2 forward over a pre-padded NHWC4 image (x4 layout:
@@ -411,8 +378,10 @@ void tfosr_conv_stem(const void* X4, const void* W224, const void* guard,
                      hipStream_t s) {
   // geometry mapped onto the generic kernel: taps=7 rows (fw=1 so rr=rs),
   // S=2, P=0 (pre-padded), "Cin"=32, pixstride=4
-  launch_conv<1, false>(X4, W224, guard, Y, /*out_bf16=*/1, N, Hp, Wp, 32,
-                        Cout, OH, OW, 2, 0, 7, 1, 4, /*fd=*/1, s);
+  const ConvLaunch a = {X4, W224, guard, Y, N, Hp, Wp, /*Cin=*/32, Cout, OH, OW,
+                        /*S=*/2, /*P=*/0, /*taps=*/7, /*fw=*/1, /*pixst=*/4,
+                        /*fd=*/1};
+  launch_conv<1, false>(a, /*out_bf16=*/1, s);
 }
 
 }  // extern "C"

@@ -75,6 +75,7 @@ gradient to the first in-bounds tap.
 """
 
 import math
+import re
 
 import numpy as np
 import pytest
@@ -1291,8 +1292,12 @@ def test_pack_model_plan():
 # 6. argument checks (each refused on the host, before any launch)
 # ===========================================================================
 
-def _rejects(fn, *args):
-    with pytest.raises(RuntimeError):
+def _rejects(fn, *args, op=None):
+    """fn(*args) raises RuntimeError (naming ``op`` where given) and leaves
+    nothing on the device: a launch on a bad pointer would fail the
+    synchronize."""
+    match = None if op is None else re.escape(op) + r"\b"
+    with pytest.raises(RuntimeError, match=match):
         fn(*args)
     torch.cuda.synchronize()
 
@@ -1438,3 +1443,220 @@ def test_bindings_pack_bf16():
     _rejects(ext.pack_bf16, d, c, n, a.cpu(), t)
     wide = torch.zeros(2 * t, dtype=BF16, device=_DEV)
     _rejects(ext.pack_bf16, d, c, n, wide[::2], t)
+
+
+# The implicit-GEMM conv family and gemm_bt, at the smallest shapes the
+# entries accept.  The stem image is 14x14: an even padded size, at which
+# the last 8-pixel K-step of a filter row ends on the image's last pixel.
+
+def _ones(*shape, dtype=BF16):
+    return torch.ones(*shape, device=_DEV, dtype=dtype)
+
+
+def _bad_acts(t):
+    """CPU, wrong dtype, NCHW-contiguous, wrong rank, empty batch."""
+    return [t.cpu(), t.float(), t.half(), t.contiguous(), t[0], t[:0]]
+
+
+def _bad_weights(w):
+    """CPU, wrong dtype, wrong rank, one row short, wrong column count."""
+    return [w.cpu(), w.float(), w.reshape(-1), w[None], w[:-1], w[:, :-32]]
+
+
+@gpu
+@requires_gpu
+@pytest.mark.parametrize("op", ["conv_mfma", "conv_mfma_stats"])
+def test_bindings_conv_mfma(op):
+    ext = _ext()
+    fn = getattr(ext, op)
+    x, wk = _cl(_ones(1, 32, 4, 4)), _ones(64, 9 * 32)
+    ok = (64, 3, 3, 1, 1, 1, -1, -1)
+
+    def y_of(r):
+        return r if op == "conv_mfma" else r[0]
+    y = y_of(fn(x, wk, *ok))
+    assert y.shape == (1, 64, 4, 4)
+    wide = _ones(64, 2 * 9 * 32)
+    assert torch.equal(y_of(fn(x, wide[:, ::2], *ok)), y)   # strided view
+    assert y_of(fn(x, wk, 64, 3, 3, 1, 1, 1, 2, 3)).shape == (1, 64, 2, 3)
+    for bad in _bad_acts(x) + [_cl(_ones(1, 16, 4, 4))]:    # Cin % 32
+        _rejects(fn, bad, wk, *ok, op=op)
+    for bad in _bad_weights(wk):
+        _rejects(fn, x, bad, *ok, op=op)
+    # Cout, fh, fw, S, P, D, OH, OW
+    for geom in ((0, 3, 3, 1, 1, 1, -1, -1), (63, 3, 3, 1, 1, 1, -1, -1),
+                 (65, 3, 3, 1, 1, 1, -1, -1), (64, 3, 3, 0, 1, 1, -1, -1),
+                 (64, 3, 3, -1, 1, 1, -1, -1), (64, 3, 3, 1, -1, 1, -1, -1),
+                 (64, 3, 3, 1, 1, 0, -1, -1), (64, 3, 3, 1, 1, 3, -1, -1),
+                 (64, 0, 3, 1, 1, 1, -1, -1), (64, 3, 0, 1, 1, 1, -1, -1),
+                 (64, 1, 3, 1, 1, 1, -1, -1),        # wk has 9 taps, not 3
+                 (64, 3, 3, 1, 1, 1, 0, 4), (64, 3, 3, 1, 1, 1, 4, 0),
+                 (64, 3, 3, 1, 1, 1, 4, -1), (64, 3, 3, 1, 1, 1, 1 << 31, 4),
+                 (64, 5, 5, 1, 0, 1, -1, -1)):       # 5x5 on 4x4, wrong wk
+        _rejects(fn, x, wk, *geom, op=op)
+    w25 = _ones(64, 25 * 32)
+    _rejects(fn, x, w25, 64, 5, 5, 1, 0, 1, -1, -1, op=op)   # does not fit
+    w64 = _ones(64, 64 * 32)
+    _rejects(fn, x, w64, 64, 8, 8, 1, 4, 1, -1, -1, op=op)   # 64 taps > 49
+
+
+@gpu
+@requires_gpu
+def test_bindings_conv_mfma_acc():
+    ext = _ext()
+    op = "conv_mfma_acc"
+    x, wk = _cl(_ones(1, 32, 4, 4)), _ones(64, 9 * 32)
+    out = _cl(torch.zeros(1, 64, 4, 4, device=_DEV, dtype=BF16))
+    ok = (3, 3, 1, 1, 1)
+    assert ext.conv_mfma_acc(x, wk, out, *ok) is out
+    for bad in _bad_acts(x) + [_cl(_ones(1, 16, 4, 4))]:
+        _rejects(ext.conv_mfma_acc, bad, wk, out, *ok, op=op)
+    for bad in _bad_weights(wk):
+        _rejects(ext.conv_mfma_acc, x, bad, out, *ok, op=op)
+    other_batch = _cl(torch.zeros(2, 64, 4, 4, device=_DEV, dtype=BF16))
+    for bad in _bad_acts(out) + [other_batch]:
+        _rejects(ext.conv_mfma_acc, x, wk, bad, *ok, op=op)
+    for geom in ((3, 3, 0, 1, 1), (3, 3, 1, -1, 1), (3, 3, 1, 1, 0),
+                 (3, 3, 1, 1, 3), (0, 3, 1, 1, 1), (1, 3, 1, 1, 1)):
+        _rejects(ext.conv_mfma_acc, x, wk, out, *geom, op=op)
+
+
+@gpu
+@requires_gpu
+def test_bindings_conv_par():
+    ext = _ext()
+    op = "conv_par"
+    x = _cl(_ones(1, 32, 4, 4))
+    w1, w2 = _ones(64, 32), _ones(64, 2 * 32)
+    out = _cl(torch.zeros(1, 64, 8, 8, device=_DEV, dtype=BF16))
+    # 3x3 stride-2 dgrad, padding 1: the classes (even, even) and (odd, even)
+    assert ext.conv_par(x, w1, out, [1], [1], 1, False) is out
+    ext.conv_par(x, w2, out, [0, 2], [1, 1], 1, False)
+    for bad in _bad_acts(x) + [_cl(_ones(1, 16, 4, 4))]:
+        _rejects(ext.conv_par, bad, w1, out, [1], [1], 1, False, op=op)
+    for bad in _bad_weights(w1):
+        _rejects(ext.conv_par, x, bad, out, [1], [1], 1, False, op=op)
+    other_batch = _cl(torch.zeros(2, 64, 8, 8, device=_DEV, dtype=BF16))
+    for bad in _bad_acts(out) + [other_batch]:
+        _rejects(ext.conv_par, x, w1, bad, [1], [1], 1, False, op=op)
+    _rejects(ext.conv_par, x, w1, out, [1], [1], -1, False, op=op)
+    _rejects(ext.conv_par, x, w1, out, [16], [1], 1, False, op=op)
+    _rejects(ext.conv_par, x, w1, out, [1], [16], 1, False, op=op)
+    _rejects(ext.conv_par, x, w1, out, [-1], [1], 1, False, op=op)
+    _rejects(ext.conv_par, x, w2, out, [0, 1], [1, 1], 1, False, op=op)
+    _rejects(ext.conv_par, x, w2, out, [0, 2], [1, 2], 1, False, op=op)
+    _rejects(ext.conv_par, x, w2, out, [0, 2], [1], 1, False, op=op)
+    _rejects(ext.conv_par, x, w1, out, [1], [1, 1], 1, False, op=op)
+    _rejects(ext.conv_par, x, w1, out, [], [], 1, False, op=op)
+    w9 = _ones(64, 9 * 32)
+    _rejects(ext.conv_par, x, w9, out, [1] * 9, [1] * 9, 1, False, op=op)
+    _rejects(ext.conv_par, x, w1, out, [0, 2], [1, 1], 1, False, op=op)
+
+
+@gpu
+@requires_gpu
+def test_bindings_conv_stem():
+    ext = _ext()
+    x4, w224 = _cl(_ones(1, 4, 14, 14)), _ones(64, 224)
+    assert ext.conv_stem(x4, w224, 64).shape == (1, 64, 4, 4)
+    for bad in _bad_acts(x4) + [_cl(_ones(1, 8, 14, 14)),
+                                _cl(_ones(1, 4, 6, 14)),
+                                _cl(_ones(1, 4, 14, 6))]:
+        _rejects(ext.conv_stem, bad, w224, 64, op="conv_stem")
+    for bad in _bad_weights(w224):
+        _rejects(ext.conv_stem, x4, bad, 64, op="conv_stem")
+    for cout in (0, -64, 63, 65):
+        _rejects(ext.conv_stem, x4, w224, cout, op="conv_stem")
+
+    op = "conv_stem_wrw"
+    dy = _cl(_ones(1, 64, 4, 4))
+    assert ext.conv_stem_wrw(dy, x4).shape == (64, 224)
+    for bad in _bad_acts(x4) + [_cl(_ones(1, 8, 14, 14)),
+                                _cl(_ones(2, 4, 14, 14)),
+                                _cl(_ones(1, 4, 16, 14)),
+                                _cl(_ones(1, 4, 14, 6))]:
+        _rejects(ext.conv_stem_wrw, dy, bad, op=op)
+    for bad in _bad_acts(dy) + [_cl(_ones(2, 64, 4, 4)),
+                                _cl(_ones(1, 64, 5, 4)),
+                                _cl(_ones(1, 64, 4, 3)),
+                                _cl(_ones(1, 60, 4, 4))]:
+        _rejects(ext.conv_stem_wrw, bad, x4, op=op)
+
+
+@gpu
+@requires_gpu
+@pytest.mark.parametrize("op", ["conv_wrw2", "conv_wrw"])
+def test_bindings_conv_wrw(op):
+    ext = _ext()
+    fn = getattr(ext, op)
+    # conv_wrw2(dy, x, R, S_f, stride, P); conv_wrw(dy, x, R, S, P), stride 1
+    tail = (lambda R, S, P, stride=1: (R, S, stride, P)) \
+        if op == "conv_wrw2" else (lambda R, S, P, stride=1: (R, S, P))
+    x, dy = _cl(_ones(1, 32, 4, 4)), _cl(_ones(1, 64, 4, 4))
+    assert fn(dy, x, *tail(3, 3, 1)).shape == (64, 9 * 32)
+    assert fn(dy, x, *tail(1, 1, 0)).shape == (64, 32)
+    for bad in _bad_acts(x) + [_cl(_ones(1, 36, 4, 4)),     # Cin % 8
+                               _cl(_ones(2, 32, 4, 4)),
+                               _cl(_ones(1, 32, 5, 4))]:
+        _rejects(fn, dy, bad, *tail(3, 3, 1), op=op)
+    for bad in _bad_acts(dy) + [_cl(_ones(1, 60, 4, 4)),    # Cout % 8
+                                _cl(_ones(2, 64, 4, 4)),
+                                _cl(_ones(1, 64, 3, 4)),
+                                _cl(_ones(1, 64, 4, 5))]:
+        _rejects(fn, bad, x, *tail(3, 3, 1), op=op)
+    _rejects(fn, dy, x, *tail(3, 3, -1), op=op)
+    _rejects(fn, dy, x, *tail(3, 3, 0), op=op)       # natural size is 2x2
+    _rejects(fn, dy, x, *tail(0, 3, 1), op=op)
+    _rejects(fn, dy, x, *tail(1, 1, 1), op=op)       # 1x1, padded: 6x6
+    if op == "conv_wrw2":
+        _rejects(fn, dy, x, *tail(3, 3, 1, stride=0), op=op)
+        _rejects(fn, dy, x, *tail(3, 3, 1, stride=-2), op=op)
+        _rejects(fn, dy, x, *tail(3, 3, 1, stride=2), op=op)   # 2x2
+        _rejects(fn, dy, x, *tail(2, 2, 1), op=op)   # neither 1x1 nor 3x3
+
+
+@gpu
+@requires_gpu
+def test_bindings_gemm_bt():
+    ext = _ext()
+    a, b = _ones(64, 32), _ones(64, 32)
+    for out_bf16 in (False, True):
+        c = ext.gemm_bt(a, b, out_bf16)
+        assert c.shape == (64, 64) and c.dtype == (BF16 if out_bf16 else FP32)
+        assert bool((c == 32).all())
+    assert bool((ext.gemm_bt(a[:, :24], b[:, :24], False) == 24).all())
+    bads = [a.cpu(), a.float(), a.half(), a[0], a[None], a[:0], a[:, :0],
+            a[:, :16]]
+    for bad in bads:
+        _rejects(ext.gemm_bt, bad, b, False, op="gemm_bt")
+        _rejects(ext.gemm_bt, a, bad, True, op="gemm_bt")
+    _rejects(ext.gemm_bt, a.cpu(), b.cpu(), False, op="gemm_bt")
+
+    bt = b.t().contiguous()                               # [K, N]
+    assert bool((ext.gemm_bf16(a, bt) == 32).all())
+    for bad in bads:
+        _rejects(ext.gemm_bf16, bad, bt, op="gemm_bf16")
+    for bad in (bt.cpu(), bt.float(), bt[0], bt[None], bt[:16], bt[:, :0]):
+        _rejects(ext.gemm_bf16, a, bad, op="gemm_bf16")
+
+
+@gpu
+@requires_gpu
+def test_bindings_mfma_probe():
+    ext = _ext()
+    a = torch.zeros(64, 8, dtype=torch.int16, device=_DEV)
+    assert ext.mfma_probe(a, a).shape == (64, 4)
+    for bad in (a.cpu(), a.int(), a.view(BF16), a[:32], a.reshape(-1)):
+        _rejects(ext.mfma_probe, bad, a, op="mfma_probe")
+        _rejects(ext.mfma_probe, a, bad, op="mfma_probe")
+    _rejects(ext.mfma_probe, a.cpu(), a.cpu(), op="mfma_probe")
+
+
+@gpu
+@requires_gpu
+def test_bindings_surface():
+    """conv3x3_fwd left with its launcher; the version moved with it."""
+    from tensorflowonspark_amd.ops import API_VERSION
+    ext = _ext()
+    assert not hasattr(ext, "conv3x3_fwd")
+    assert ext.api_version() == API_VERSION
