@@ -86,6 +86,14 @@ void tfosr_convt_head_dgrad(const void*, const float*, void*, int, int, int,
                             int, int, hipStream_t);
 void tfosr_convt_head_wrw(const void*, const void*, float*, float*, float*,
                           int, int, int, int, int, hipStream_t);
+void tfosr_upsample_bilinear_info(int*, int*, int*, int*, int*, int*, int*,
+                                  int*, int*);
+void tfosr_upsample_bilinear_plan(int, int, int, int, int, int, int, int*,
+                                  int*, int*, long*, int*, int*, long*);
+void tfosr_upsample_bilinear_fwd(const void*, void*, int, int, int, int, int,
+                                 int, int, int, hipStream_t);
+void tfosr_upsample_bilinear_bwd(const void*, void*, int, int, int, int, int,
+                                 int, int, int, hipStream_t);
 void tfosr_conv_mfma(const void*, const void*, const void*, void*, int, int,
                      int, int, int, int, int, int, int, int, int, int, int,
                      int, int, hipStream_t);
@@ -1155,7 +1163,7 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 10
+#define TFOSR_API_VERSION 11
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
@@ -1788,8 +1796,144 @@ static std::tuple<at::Tensor, at::Tensor> convt_head_wrw(at::Tensor dy,
   return {dw, db};
 }
 
+// ---------------------------------------------------------------------------
+// Bilinear upsampling (csrc/upsample_bilinear.hip): channels_last bf16 or
+// fp32, C in [1, 2048], upscale or identity on both axes
+// ---------------------------------------------------------------------------
+
+struct UbPlan {
+  int fwd_cc, fwd_ph, fwd_pw, bwd_cc, bwd_p;
+  long fwd_tiles, bwd_tiles;
+};
+
+static int ub_max_c() {
+  int v[9];
+  tfosr_upsample_bilinear_info(v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6,
+                               v + 7, v + 8);
+  return v[8];
+}
+
+// The tensor as the kernels take it. Returns true when it is empty.
+static bool ub_check_act(const char* op, const char* name,
+                         const at::Tensor& t) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.dim() == 4, op, ": ", name, " must be 4-D (N, C, H, W), got ",
+              t.dim(), "-D");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 ||
+                  t.scalar_type() == at::kFloat,
+              op, ": ", name, " must be bf16 or fp32, got ", t.scalar_type());
+  TORCH_CHECK(t.size(2) >= 1 && t.size(3) >= 1, op, ": ", name,
+              " must have at least one row and column, got ", t.sizes());
+  if (t.numel() == 0) return true;
+  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name,
+              " must be channels_last-contiguous");
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+              " must be 16-byte aligned");
+  TORCH_CHECK(t.size(1) <= ub_max_c(), op, ": C=", t.size(1),
+              " must be at most ", ub_max_c());
+  return false;
+}
+
+// Sizes of the small (in) and large (out) image of one call; fills the plan.
+static UbPlan ub_check_sizes(const char* op, long N, long C, long Hin,
+                             long Win, long Hout, long Wout, bool align,
+                             int itemsize) {
+  TORCH_CHECK(Hout >= 1 && Hout <= INT_MAX && Wout >= 1 && Wout <= INT_MAX &&
+                  Hin >= 1 && Hin <= INT_MAX && Win >= 1 && Win <= INT_MAX,
+              op, ": sizes must be in [1, ", INT_MAX, "], got ", Hin, "x", Win,
+              " and ", Hout, "x", Wout);
+  TORCH_CHECK(Hout >= Hin && Wout >= Win, op, ": upscale only, got ", Hin,
+              "x", Win, " -> ", Hout, "x", Wout);
+  TORCH_CHECK(N * Hout <= INT_MAX / Wout, op, ": ", N, "x", Hout, "x", Wout,
+              " pixels, more than the kernels index");
+  UbPlan p{};
+  if (C == 0) return p;
+  tfosr_upsample_bilinear_plan((int)C, (int)Hin, (int)Win, (int)Hout,
+                               (int)Wout, align, itemsize, &p.fwd_cc,
+                               &p.fwd_ph, &p.fwd_pw, &p.fwd_tiles, &p.bwd_cc,
+                               &p.bwd_p, &p.bwd_tiles);
+  TORCH_CHECK(N == 0 || (p.fwd_tiles <= INT_MAX / N &&
+                         p.bwd_tiles <= INT_MAX / N),
+              op, ": ", N, " images of ", p.fwd_tiles, " and ", p.bwd_tiles,
+              " tiles, more than the kernels index");
+  return p;
+}
+
+static at::Tensor upsample_bilinear_fwd(at::Tensor x, long Hout, long Wout,
+                                        bool align_corners) {
+  const char* op = "upsample_bilinear_fwd";
+  const bool empty = ub_check_act(op, "x", x);
+  const long N = x.size(0), C = x.size(1), Hin = x.size(2), Win = x.size(3);
+  ub_check_sizes(op, N, C, Hin, Win, Hout, Wout, align_corners,
+                 (int)x.element_size());
+  auto y = at::empty({N, C, Hout, Wout}, x.options(),
+                     at::MemoryFormat::ChannelsLast);
+  if (empty) return y;
+  tfosr_upsample_bilinear_fwd(x.data_ptr(), y.data_ptr(),
+                              x.scalar_type() == at::kBFloat16, (int)N, (int)C,
+                              (int)Hin, (int)Win, (int)Hout, (int)Wout,
+                              align_corners, cur_stream());
+  return y;
+}
+
+static at::Tensor upsample_bilinear_bwd(at::Tensor dy, long Hin, long Win,
+                                        bool align_corners) {
+  const char* op = "upsample_bilinear_bwd";
+  const bool empty = ub_check_act(op, "dy", dy);
+  const long N = dy.size(0), C = dy.size(1), Hout = dy.size(2),
+             Wout = dy.size(3);
+  ub_check_sizes(op, N, C, Hin, Win, Hout, Wout, align_corners,
+                 (int)dy.element_size());
+  auto dx = at::empty({N, C, Hin, Win}, dy.options(),
+                      at::MemoryFormat::ChannelsLast);
+  if (empty) return dx;
+  tfosr_upsample_bilinear_bwd(dy.data_ptr(), dx.data_ptr(),
+                              dy.scalar_type() == at::kBFloat16, (int)N,
+                              (int)C, (int)Hin, (int)Win, (int)Hout, (int)Wout,
+                              align_corners, cur_stream());
+  return dx;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("api_version", []() { return TFOSR_API_VERSION; });
+  m.def("upsample_bilinear_fwd", &upsample_bilinear_fwd, py::arg("x"),
+        py::arg("Hout"), py::arg("Wout"), py::arg("align_corners"));
+  m.def("upsample_bilinear_bwd", &upsample_bilinear_bwd, py::arg("dy"),
+        py::arg("Hin"), py::arg("Win"), py::arg("align_corners"));
+  m.def("upsample_bilinear_info", []() {
+    int block, max_grid, fh, fw, bh, bw, br, lds, max_c;
+    tfosr_upsample_bilinear_info(&block, &max_grid, &fh, &fw, &bh, &bw, &br,
+                                 &lds, &max_c);
+    py::dict d;
+    d["block"] = block;
+    d["max_grid"] = max_grid;
+    d["fwd_tile_h"] = fh;
+    d["fwd_tile_w"] = fw;
+    d["bwd_tile_h"] = bh;
+    d["bwd_tile_w"] = bw;
+    d["bwd_rows"] = br;
+    d["lds"] = lds;
+    d["max_c"] = max_c;
+    return d;
+  });
+  m.def("upsample_bilinear_plan", [](long C, long Hin, long Win, long Hout,
+                                     long Wout, bool align_corners,
+                                     long itemsize) {
+    TORCH_CHECK(C >= 1 && C <= ub_max_c() && (itemsize == 2 || itemsize == 4),
+                "upsample_bilinear_plan: C must be in [1, ", ub_max_c(),
+                "] and itemsize 2 or 4");
+    const UbPlan p = ub_check_sizes("upsample_bilinear_plan", 1, C, Hin, Win,
+                                    Hout, Wout, align_corners, (int)itemsize);
+    py::dict d;
+    d["fwd_cc"] = p.fwd_cc;
+    d["fwd_patch_h"] = p.fwd_ph;
+    d["fwd_patch_w"] = p.fwd_pw;
+    d["fwd_tiles"] = p.fwd_tiles;
+    d["bwd_cc"] = p.bwd_cc;
+    d["bwd_cols"] = p.bwd_p;
+    d["bwd_tiles"] = p.bwd_tiles;
+    return d;
+  });
   m.def("bn_fwd_train", &bn_fwd_train);
   m.def("bn_fwd_eval", &bn_fwd_eval);
   m.def("bn_bwd", &bn_bwd);

@@ -14,11 +14,10 @@ other widths (24 .. 960) the vectorised row tier.
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
-from ..ops.modules import (ConvTranspose2dHead, ConvTranspose2dMFMA,
-                           DepthwiseConv3x3, DilatedConv3x3, FusedBN,
-                           FusedBNAdd, FusedBNReLU)
+from ..ops.modules import (BilinearUpsample, ConvTranspose2dHead,
+                           ConvTranspose2dMFMA, DepthwiseConv3x3,
+                           DilatedConv3x3, FusedBN, FusedBNAdd, FusedBNReLU)
 from .resnet import Bottleneck, ResNet, _maybe_pack_weights
 
 
@@ -177,13 +176,13 @@ class ASPP(nn.Module):
                                   nn.Conv2d(cin, cout, 1, bias=False),
                                   nn.ReLU(inplace=True))
         self.project = ConvBNReLU(cout * (2 + len(rates)), cout, k=1)
+        # no parameters: state_dict keys and the RNG draw order are unchanged
+        self.upsample = BilinearUpsample(align_corners=False)
 
     def forward(self, x):
         size = x.shape[-2:]
         feats = [b(x) for b in self.branches]
-        p = F.interpolate(self.pool(x), size=size, mode="bilinear",
-                          align_corners=False)
-        feats.append(p)
+        feats.append(self.upsample(self.pool(x), size))
         return self.project(torch.cat(feats, dim=1))
 
 
@@ -237,13 +236,13 @@ class DeepLabV3(nn.Module):
         self.backbone = DilatedResNet50()
         self.aspp = ASPP(2048, 256)
         self.classifier = nn.Conv2d(256, num_classes, 1)
+        self.upsample = BilinearUpsample(align_corners=False)
 
     def forward(self, x):
         size = x.shape[-2:]
         feats = self.backbone(x)
         out = self.classifier(self.aspp(feats))
-        return F.interpolate(out, size=size, mode="bilinear",
-                             align_corners=False)
+        return self.upsample(out, size)
 
 
 def deeplabv3_resnet50(num_classes=21):

@@ -7,6 +7,7 @@ reference implementation the numerics tests compare against.
 """
 
 import os
+from typing import List
 
 import torch
 import torch.nn as nn
@@ -1329,6 +1330,147 @@ class ConvTranspose2dHead(nn.ConvTranspose2d):
         new.weight = self.weight
         if self.bias is not None:
             new.bias = self.bias
+        new.train(self.training)
+        return new
+
+
+# ---------------------------------------------------------------------------
+# Bilinear upsampling (csrc/upsample_bilinear.hip)
+# ---------------------------------------------------------------------------
+
+_UB_MAX_C = 2048
+
+
+def _ub_table():
+    """(N, C, Hin, Win, Hout, Wout, fwd, bwd) per measured shape: True where
+    tools/upsample_bench.py measured the in-tree kernel faster than the
+    library on the MI355X by more than either side's spread
+    (docs/performance.md "Bilinear upsampling"; the run is
+    profiles/upsample_bench.json)."""
+    T = True
+    return (
+        (32, 21, 32, 32, 512, 512, T, T),    # DeepLabV3 head
+        (32, 256, 1, 1, 32, 32, T, T),       # ASPP pool branch
+    )
+
+
+def _ub_auto(direction, N, C, Hin, Win, Hout, Wout):
+    """TFOS_UPSAMPLE=auto policy: is ``direction`` ('fwd' or 'bwd') routed
+    in-tree? A shape that was not measured takes the decision of the measured
+    one whose output element count is nearest in ratio: both directions
+    stream the large tensor."""
+    rows = _ub_table()
+    want = float(max(1, N * C * Hout * Wout))
+
+    def dist(r):
+        have = float(r[0] * r[1] * r[4] * r[5])
+        return max(have / want, want / have)
+
+    exact = [r for r in rows if r[:6] == (N, C, Hin, Win, Hout, Wout)]
+    row = exact[0] if exact else min(rows, key=dist)
+    return row[6 + ("fwd", "bwd").index(direction)]
+
+
+def _ub_route(N, C, Hin, Win, Hout, Wout):
+    """(fwd_in_tree, bwd_in_tree) for TFOS_UPSAMPLE, or None for the plain
+    library call."""
+    mode = os.environ.get("TFOS_UPSAMPLE", "auto")
+    if mode == "aten":
+        return None
+    if mode == "hip":
+        return True, True
+    if mode != "auto":
+        raise ValueError("TFOS_UPSAMPLE must be auto, hip or aten, got "
+                         + repr(mode))
+    route = tuple(_ub_auto(d, N, C, Hin, Win, Hout, Wout)
+                  for d in ("fwd", "bwd"))
+    return route if any(route) else None
+
+
+class _BilinearUpsampleFn(torch.autograd.Function):
+    """Bilinear resize of a channels_last bf16 or fp32 tensor; forward and
+    backward each run in-tree or through the library as their flag says."""
+
+    @staticmethod
+    def forward(ctx, x, Hout, Wout, align_corners, fwd_in_tree, bwd_in_tree):
+        if fwd_in_tree:
+            y = get_ext(required=True).upsample_bilinear_fwd(
+                x, Hout, Wout, align_corners)
+        else:
+            y = F.interpolate(x, size=(Hout, Wout), mode="bilinear",
+                              align_corners=align_corners)
+        ctx.geom = (tuple(x.shape), x.dtype, align_corners, bwd_in_tree)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        shape, dtype, align_corners, bwd_in_tree = ctx.geom
+        # an expanded (stride-0) gradient, as from y.sum().backward(),
+        # becomes a real channels_last tensor here
+        dy = dy.to(dtype).contiguous(memory_format=torch.channels_last)
+        if bwd_in_tree:
+            dx = get_ext(required=True).upsample_bilinear_bwd(
+                dy, shape[2], shape[3], align_corners)
+        else:
+            dx = torch.ops.aten.upsample_bilinear2d_backward(
+                dy, list(dy.shape[2:]), list(shape), align_corners, None,
+                None)
+        return dx, None, None, None, None, None
+
+
+def bilinear_upsample(x, size, align_corners=False):
+    """``F.interpolate(x, size=size, mode="bilinear")`` with the in-tree
+    kernels where they apply: 4-D channels_last-contiguous GPU tensors in
+    bf16 or fp32 with at most 2048 channels and an output no smaller than the
+    input on either axis. Backend select via TFOS_UPSAMPLE, read at call
+    time: 'auto' (default: forward and backward each go in-tree only where
+    measured faster than the library, see _ub_auto), 'hip' (both in-tree
+    wherever eligible), 'aten' (library call). Everything else (CPU,
+    NCHW-contiguous, a downscale, other dtypes, more channels) is the
+    library call unchanged."""
+    if isinstance(size, int):
+        size = (size, size)
+    Hout, Wout = int(size[0]), int(size[1])
+    route = _ub_route(*((x.shape if x.dim() == 4 else (0, 0, 0, 0))
+                        + (Hout, Wout)))
+    if route is not None and x.is_cuda and x.dim() == 4 \
+            and x.dtype in (torch.bfloat16, torch.float32) \
+            and 1 <= x.shape[1] <= _UB_MAX_C and x.numel() > 0 \
+            and Hout >= x.shape[2] >= 1 and Wout >= x.shape[3] >= 1 \
+            and x.is_contiguous(memory_format=torch.channels_last) \
+            and x.data_ptr() % 16 == 0 \
+            and get_ext(required=True) is not None:
+        return _BilinearUpsampleFn.apply(x, Hout, Wout, bool(align_corners),
+                                         *route)
+    return F.interpolate(x, size=(Hout, Wout), mode="bilinear",
+                         align_corners=align_corners)
+
+
+class _PlainBilinearUpsample(nn.Module):
+    """What the scripter sees in place of BilinearUpsample."""
+
+    def __init__(self, align_corners):
+        super().__init__()
+        self.align_corners = align_corners
+
+    def forward(self, x, size: List[int]):
+        return F.interpolate(x, size=size, mode="bilinear",
+                             align_corners=self.align_corners)
+
+
+class BilinearUpsample(nn.Module):
+    """Parameter-free module around bilinear_upsample: ``forward(x, size)``."""
+
+    def __init__(self, align_corners=False):
+        super().__init__()
+        self.align_corners = align_corners
+
+    def forward(self, x, size):
+        return bilinear_upsample(x, size, self.align_corners)
+
+    def __prepare_scriptable__(self):
+        _SCRIPT_CLONE_KEEPALIVE.append(self)
+        new = _PlainBilinearUpsample(self.align_corners)
         new.train(self.training)
         return new
 
