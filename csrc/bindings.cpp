@@ -86,6 +86,10 @@ void tfosr_convt_head_dgrad(const void*, const float*, void*, int, int, int,
                             int, int, hipStream_t);
 void tfosr_convt_head_wrw(const void*, const void*, float*, float*, float*,
                           int, int, int, int, int, hipStream_t);
+void tfosr_pwconv_info(int*, int*, int*);
+void tfosr_pwconv_plan(long, int, int, int*, long*, int*, int*, int*, int*);
+hipError_t tfosr_pwconv_gemm(const void*, const void*, int, void*, long, int,
+                             int, int, hipStream_t);
 void tfosr_upsample_bilinear_info(int*, int*, int*, int*, int*, int*, int*,
                                   int*, int*);
 void tfosr_upsample_bilinear_plan(int, int, int, int, int, int, int, int*,
@@ -1163,7 +1167,7 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 11
+#define TFOSR_API_VERSION 12
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
@@ -1797,6 +1801,93 @@ static std::tuple<at::Tensor, at::Tensor> convt_head_wrw(at::Tensor dy,
 }
 
 // ---------------------------------------------------------------------------
+// Pointwise convs (csrc/pwconv.hip): 1x1, stride 1, no bias, channel counts
+// that are multiples of 8 in [8, 960], bf16 channels_last; the weight is the
+// module's contiguous [Cout, Cin, 1, 1] parameter, fp32 or bf16
+// ---------------------------------------------------------------------------
+
+struct PwPlan {
+  int tile_m, panels, ppp, grid, lds_bytes;
+  long m_tiles;
+};
+
+static PwPlan pw_plan(long M, long K, long Co) {
+  PwPlan p;
+  tfosr_pwconv_plan(M, (int)K, (int)Co, &p.tile_m, &p.m_tiles, &p.panels,
+                    &p.ppp, &p.grid, &p.lds_bytes);
+  return p;
+}
+
+static void pw_check_channels(const char* op, const char* name, long C) {
+  int tile_m, max_grid, max_c;
+  tfosr_pwconv_info(&tile_m, &max_grid, &max_c);
+  TORCH_CHECK(C % 8 == 0 && C >= 8 && C <= max_c, op, ": ", name, "=", C,
+              " must be a multiple of 8 in [8, ", max_c, "]");
+}
+
+// An activation or gradient as the kernels take it: cv_check_act, but an
+// empty tensor passes (returns true: nothing to launch), the base must sit
+// on the 16 B grid of the vector accesses, and N*H*W must fit the kernels'
+// 32-bit pixel index.
+static bool pw_check_act(const char* op, const char* name,
+                         const at::Tensor& t) {
+  if (t.is_cuda() && t.dim() == 4 && t.scalar_type() == at::kBFloat16 &&
+      t.numel() == 0)
+    return true;
+  cv_check_act(op, name, t, 8);
+  pw_check_channels(op, name, t.size(1));
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+              " must be 16-byte aligned");
+  TORCH_CHECK(t.numel() / t.size(1) <= INT_MAX, op, ": ", name, " has ",
+              t.numel() / t.size(1), " pixels, more than the 32-bit pixel "
+              "index holds");
+  return false;
+}
+
+static void pw_check_weight(const char* op, const at::Tensor& w,
+                            const at::Tensor& act) {
+  cv_check_device(op, "weight", w, act);
+  TORCH_CHECK((w.scalar_type() == at::kFloat ||
+               w.scalar_type() == at::kBFloat16) &&
+                  w.dim() == 4 && w.size(2) == 1 && w.size(3) == 1 &&
+                  w.is_contiguous(),
+              op, ": weight must be the contiguous fp32 or bf16 "
+              "[Cout,Cin,1,1] parameter, got ", w.scalar_type(), " ",
+              w.sizes());
+  pw_check_channels(op, "Cout", w.size(0));
+  pw_check_channels(op, "Cin", w.size(1));
+}
+
+// fwd (transposed = false): y[N, Cout, H, W] from x[N, Cin, H, W]; dgrad
+// (transposed = true): dx[N, Cin, H, W] from dy[N, Cout, H, W]
+static at::Tensor pw_gemm(const char* op, const char* name, at::Tensor in,
+                          at::Tensor w, bool transposed) {
+  const bool empty = pw_check_act(op, name, in);
+  pw_check_weight(op, w, in);
+  const long K = w.size(transposed ? 0 : 1), Co = w.size(transposed ? 1 : 0);
+  TORCH_CHECK(in.size(1) == K, op, ": weight must be [Cout,Cin,1,1] with ",
+              transposed ? "Cout=" : "Cin=", in.size(1), ", got ", w.sizes());
+  auto out = at::empty({in.size(0), Co, in.size(2), in.size(3)}, in.options(),
+                       at::MemoryFormat::ChannelsLast);
+  if (empty) return out;
+  const long M = in.size(0) * in.size(2) * in.size(3);
+  const hipError_t err = tfosr_pwconv_gemm(
+      in.data_ptr(), w.data_ptr(), w.scalar_type() == at::kBFloat16,
+      out.data_ptr(), M, (int)K, (int)Co, transposed, cur_stream());
+  TORCH_CHECK(err == hipSuccess, op, ": launch failed: ",
+              hipGetErrorString(err));
+  return out;
+}
+
+static at::Tensor pwconv_fwd(at::Tensor x, at::Tensor w) {
+  return pw_gemm("pwconv_fwd", "x", x, w, false);
+}
+
+static at::Tensor pwconv_dgrad(at::Tensor dy, at::Tensor w) {
+  return pw_gemm("pwconv_dgrad", "dy", dy, w, true);
+}
+
+// ---------------------------------------------------------------------------
 // Bilinear upsampling (csrc/upsample_bilinear.hip): channels_last bf16 or
 // fp32, C in [1, 2048], upscale or identity on both axes
 // ---------------------------------------------------------------------------
@@ -2168,6 +2259,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     d["slab"] = slab;
     return d;
   }, py::arg("M"), py::arg("Cin"), py::arg("Cout"));
+
+  m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"));
+  m.def("pwconv_dgrad", &pwconv_dgrad, py::arg("dy"), py::arg("w"));
+  m.def("pwconv_info", []() {
+    int tile_m, max_grid, max_c;
+    tfosr_pwconv_info(&tile_m, &max_grid, &max_c);
+    py::dict d;
+    d["tile_m"] = tile_m;
+    d["max_grid"] = max_grid;
+    d["max_channels"] = max_c;
+    return d;
+  });
+  // M pixels, Ci contracted (fwd: Cin, dgrad: Cout), Co produced; tile_m is
+  // this shape's own M tile.
+  m.def("pwconv_plan", [](long M, long Ci, long Co) {
+    TORCH_CHECK(M > 0 && M <= INT_MAX, "pwconv_plan: M must be in [1, ",
+                INT_MAX, "]");
+    pw_check_channels("pwconv_plan", "Ci", Ci);
+    pw_check_channels("pwconv_plan", "Co", Co);
+    const PwPlan p = pw_plan(M, Ci, Co);
+    py::dict d;
+    d["tile_m"] = p.tile_m;
+    d["m_tiles"] = p.m_tiles;
+    d["panels"] = p.panels;
+    d["grid"] = p.grid;
+    d["lds_bytes"] = p.lds_bytes;
+    return d;
+  }, py::arg("M"), py::arg("Ci"), py::arg("Co"));
 
   // native TFRecord codec (CPU): bulk scan/write with HW CRC32-C
   m.def("crc32c", [](py::bytes data) {

@@ -17,7 +17,8 @@ import torch.nn as nn
 
 from ..ops.modules import (BilinearUpsample, ConvTranspose2dHead,
                            ConvTranspose2dMFMA, DepthwiseConv3x3,
-                           DilatedConv3x3, FusedBN, FusedBNAdd, FusedBNReLU)
+                           DilatedConv3x3, FusedBN, FusedBNAdd, FusedBNReLU,
+                           PointwiseConv)
 from .resnet import Bottleneck, ResNet, _maybe_pack_weights
 
 
@@ -33,6 +34,11 @@ class ConvBNReLU(nn.Sequential):
             # depthwise 3x3: same parameters and init as the nn.Conv2d
             # below, routed to the in-tree streaming kernels (TFOS_DW)
             conv = DepthwiseConv3x3(cin, stride=stride)
+        elif k == 1 and groups == 1 and stride == 1 and dilation == 1 \
+                and max(cin, cout) <= 960:
+            # pointwise: same parameters and init as the nn.Conv2d below,
+            # routed to the in-tree streaming kernels (TFOS_PW)
+            conv = PointwiseConv(cin, cout)
         else:
             conv = nn.Conv2d(cin, cout, k, stride, pad, groups=groups,
                              dilation=dilation, bias=False)
@@ -51,7 +57,7 @@ class InvertedResidual(nn.Module):
             layers.append(ConvBNReLU(cin, hidden, k=1))
         layers += [
             ConvBNReLU(hidden, hidden, k=3, stride=stride, groups=hidden),
-            nn.Conv2d(hidden, cout, 1, bias=False),
+            PointwiseConv(hidden, cout),
             # the project BN is linear; with a skip it adds the block input in
             # the same pass (same parameter and buffer names as BatchNorm2d)
             FusedBNAdd(cout) if self.use_res else FusedBN(cout),

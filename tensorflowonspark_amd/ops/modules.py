@@ -1060,6 +1060,179 @@ class DepthwiseConv3x3(nn.Conv2d):
         return new
 
 
+# ---------------------------------------------------------------------------
+# Pointwise 1x1 convolution (csrc/pwconv.hip)
+# ---------------------------------------------------------------------------
+
+_PW_MAX_C = 960
+
+
+def _pw_table():
+    """(N, cin, cout, H, W, fwd, dgrad, wrw) per measured layer: fwd and
+    dgrad True where tools/pw_bench.py measured the in-tree kernel no slower
+    than the library on the MI355X, wrw 'wrw2' where conv_wrw2 was no
+    slower than the library and 'lib' elsewhere (docs/performance.md
+    "Pointwise convolutions"; the run is profiles/pw_bench.json, whose
+    "auto" column this repeats)."""
+    T, F_, W2, L = True, False, "wrw2", "lib"
+    return (
+        (64, 32, 16, 64, 64, T, T, W2),
+        (64, 16, 96, 64, 64, T, T, W2),
+        (64, 96, 24, 32, 32, T, T, W2),
+        (64, 24, 144, 32, 32, T, T, W2),
+        (64, 144, 24, 32, 32, T, T, W2),
+        (64, 144, 32, 16, 16, T, T, W2),
+        (64, 32, 192, 16, 16, T, T, W2),
+        (64, 192, 32, 16, 16, T, T, W2),
+        (64, 192, 64, 8, 8, T, T, W2),
+        (64, 64, 384, 8, 8, F_, F_, W2),
+        (64, 384, 64, 8, 8, T, T, W2),      # 0.3 % and 8 %: inside the spread
+        (64, 384, 96, 8, 8, F_, F_, W2),
+        (64, 96, 576, 8, 8, F_, F_, W2),
+        (64, 576, 96, 8, 8, F_, F_, W2),
+        (64, 576, 160, 4, 4, F_, F_, W2),
+        (64, 160, 960, 4, 4, F_, F_, W2),
+        (64, 960, 160, 4, 4, F_, F_, W2),
+        (64, 960, 320, 4, 4, F_, F_, W2),
+        (1024, 32, 16, 64, 64, T, T, L),
+        (1024, 16, 96, 64, 64, T, T, W2),
+        (1024, 96, 24, 32, 32, T, T, W2),
+        (1024, 24, 144, 32, 32, T, T, L),
+        (1024, 144, 24, 32, 32, T, T, L),
+        (1024, 144, 32, 16, 16, T, T, L),
+        (1024, 32, 192, 16, 16, T, T, L),
+        (1024, 192, 32, 16, 16, T, T, L),
+        (1024, 192, 64, 8, 8, T, T, W2),
+        (1024, 64, 384, 8, 8, F_, F_, W2),
+        (1024, 384, 64, 8, 8, F_, F_, W2),
+        (1024, 384, 96, 8, 8, F_, F_, W2),
+        (1024, 96, 576, 8, 8, F_, F_, W2),
+        (1024, 576, 96, 8, 8, F_, F_, W2),
+        (1024, 576, 160, 4, 4, F_, F_, W2),
+        (1024, 160, 960, 4, 4, F_, F_, W2),
+        (1024, 960, 160, 4, 4, F_, F_, W2),
+        (1024, 960, 320, 4, 4, F_, F_, W2),
+    )
+
+
+def _pw_auto(N, cin, cout, H, W):
+    """TFOS_PW=auto: the measured row for this layer; a shape that was not
+    measured takes the row whose M * (cin + cout), the bytes forward and
+    dgrad move, is nearest in ratio (these are streaming kernels, as in
+    _dw_auto)."""
+    rows = _pw_table()
+    want = float(max(1, N * H * W * (cin + cout)))
+
+    def dist(r):
+        have = float(r[0] * r[3] * r[4] * (r[1] + r[2]))
+        return max(have / want, want / have)
+
+    exact = [r for r in rows if r[:5] == (N, cin, cout, H, W)]
+    return (exact[0] if exact else min(rows, key=dist))[5:]
+
+
+def _pw_route(N, cin, cout, H, W):
+    """(fwd_in_tree, dgrad_in_tree, wrw) for TFOS_PW, wrw one of 'wrw2' and
+    'lib'; None for the plain library conv."""
+    mode = os.environ.get("TFOS_PW", "auto")
+    if mode == "miopen":
+        return None
+    if mode == "hip":
+        return True, True, "wrw2"
+    if mode != "auto":
+        raise ValueError("TFOS_PW must be auto, hip or miopen, got "
+                         + repr(mode))
+    route = _pw_auto(N, cin, cout, H, W)
+    return None if route == (False, False, "lib") else route
+
+
+class _PointwiseFn(torch.autograd.Function):
+    """1x1 conv on channels_last bf16 with the module's fp32 weight. Forward
+    and dgrad run in-tree or through the library as their flags say, wrw
+    through conv_wrw2 or the library; the library sees the
+    weight cast to bf16, the value the kernels round to while staging."""
+
+    @staticmethod
+    def forward(ctx, x, weight, fwd_in_tree, dgrad_in_tree, wrw):
+        if fwd_in_tree:
+            y = get_ext(required=True).pwconv_fwd(x, weight)
+        else:
+            y = F.conv2d(x, weight.to(x.dtype))
+        ctx.save_for_backward(x, weight)
+        ctx.route = (dgrad_in_tree, wrw)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dgrad_in_tree, wrw = ctx.route
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        # an expanded (stride-0) gradient, as from y.sum().backward(),
+        # becomes a real channels_last tensor here
+        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if need_dx and dgrad_in_tree:
+            dx = get_ext(required=True).pwconv_dgrad(dy, weight)
+        if need_dw and wrw == "wrw2":
+            dw = get_ext(required=True).conv_wrw2(dy, x, 1, 1, 1, 0)
+            dw = dw.view_as(weight).to(weight.dtype)
+        lib_dx = need_dx and dx is None
+        lib_dw = need_dw and dw is None
+        if lib_dx or lib_dw:
+            gx, gw, _ = torch.ops.aten.convolution_backward(
+                dy, x, weight.to(x.dtype), None, [1, 1], [0, 0], [1, 1],
+                False, [0, 0], 1, [lib_dx, lib_dw, False])
+            if lib_dx:
+                dx = gx
+            if lib_dw:
+                dw = gw.to(weight.dtype)
+        return dx, dw, None, None, None
+
+
+class PointwiseConv(nn.Conv2d):
+    """1x1 conv (stride 1, no bias) routed to the in-tree streaming kernels.
+
+    A subclass of nn.Conv2d so that parameter name, shape, the default
+    initialisation and the RNG draw order are exactly those of the
+    ``nn.Conv2d(cin, cout, 1, bias=False)`` it stands in for. Backend select
+    via TFOS_PW, read at call time: 'auto' (default: each of forward, dgrad
+    and wrw goes in-tree only where it was measured no slower than the
+    library, see _pw_auto), 'hip' (forward and dgrad in-tree, wrw through
+    conv_wrw2), 'miopen' (library conv). CPU tensors, an effective dtype other than bf16, a parameter that
+    is not fp32 and channel counts that are no multiple of 8 or exceed 960
+    stay on the library path.
+    """
+
+    def __init__(self, cin, cout, device=None, dtype=None):
+        super().__init__(cin, cout, 1, bias=False, device=device, dtype=dtype)
+
+    def forward(self, x):
+        if x.is_cuda and x.dim() == 4 and self.weight.dtype == torch.float32:
+            # under autocast the library conv would run in the autocast
+            # dtype whatever x is; so does this path
+            dt = torch.get_autocast_dtype("cuda") \
+                if torch.is_autocast_enabled("cuda") else x.dtype
+            cin, cout = self.in_channels, self.out_channels
+            N, _, H, W = x.shape
+            if (dt == torch.bfloat16 and cin % 8 == 0 and cout % 8 == 0
+                    and max(cin, cout) <= _PW_MAX_C
+                    and 0 < N * H * W < 2 ** 31):
+                route = _pw_route(N, cin, cout, H, W)
+                if route is not None and get_ext(required=True) is not None:
+                    x = x.to(dt).contiguous(memory_format=torch.channels_last)
+                    return _PointwiseFn.apply(x, self.weight, *route)
+        return super().forward(x)
+
+    def __prepare_scriptable__(self):
+        # the scripter must not compile the routed forward: hand it a plain
+        # conv that shares the weight
+        _SCRIPT_CLONE_KEEPALIVE.append(self)
+        new = nn.Conv2d(self.in_channels, self.out_channels, 1, bias=False)
+        new.weight = self.weight
+        new.train(self.training)
+        return new
+
+
 def _parity_launch(x, class_weight, out, k, pp, accum):
     """One conv_par launch per non-empty output parity class, each with only
     its valid taps; class_weight(ph, pw, rl, sl) is [OC, nr, ns, KC]."""
