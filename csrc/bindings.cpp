@@ -69,6 +69,19 @@ void tfosr_maxpool_fwd(const void*, void*, unsigned char*, int, int, int, int,
                        int, int, int, int, int, int, hipStream_t);
 void tfosr_maxpool_bwd(const void*, const unsigned char*, void*, int, int, int,
                        int, int, int, int, int, int, int, hipStream_t);
+int tfosr_bn_pool_eligible(long, long, long, long, long);
+int tfosr_bn_pool_blocks(long);
+void tfosr_bn_relu_pool_fwd(const void*, void*, unsigned char*, const float*,
+                            const float*, const float*, const float*, int, int,
+                            int, int, int, int, int, int, int, hipStream_t);
+void tfosr_bn_relu_pool_bwd_stats(const void*, const void*,
+                                  const unsigned char*, const float*,
+                                  const float*, float*, int, int, int, int, int,
+                                  int, int, int, int, int, hipStream_t);
+void tfosr_bn_relu_pool_bwd_dx(const void*, const void*, const unsigned char*,
+                               void*, const float*, const float*, const float*,
+                               const float*, const float*, int, int, int, int,
+                               int, int, int, int, int, hipStream_t);
 void tfosr_dwconv3x3_info(int*, int*, int*, int*, int*, int*, int*);
 void tfosr_dwconv3x3_wrw_plan(long, int, int*, int*, int*, int*, long*);
 void tfosr_dwconv3x3_fwd(const void*, const float*, void*, int, int, int, int,
@@ -1014,6 +1027,184 @@ std::pair<long, long> check_pool_geometry(const char* op, const at::Tensor& t,
   return {OH, OW};
 }
 
+// BatchNorm + ReLU + MaxPool2d as one op (csrc/bn_pool.hip): the ResNet stem's
+// tail in training, on bf16 channels_last tensors the NHWC fast path of
+// bn_relu.hip takes. bn_relu_pool_eligible() says whether the fused entries
+// take a tensor and never throws; callers run bn_fwd_train + maxpool_fwd
+// otherwise.
+bool bn_relu_pool_eligible(const at::Tensor& x, long K, long S, long P) {
+  if (!x.is_cuda() || x.dim() != 4 || x.scalar_type() != at::kBFloat16 ||
+      !x.is_contiguous(at::MemoryFormat::ChannelsLast))
+    return false;
+  const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  if (N < 1 || H < 1 || W < 1 || K < 1 || S < 1 || P < 0 || P > K / 2 ||
+      H + 2 * P < K || W + 2 * P < K || S > INT_MAX)
+    return false;
+  return tfosr_bn_pool_eligible(N, C, H, W, K) != 0;
+}
+
+// the checks both fused entries share; returns {OH, OW}
+static std::pair<long, long> bn_relu_pool_check(const char* op,
+                                                const at::Tensor& x, long K,
+                                                long S, long P) {
+  auto l = bn_layout(x);
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && l.nhwc, op,
+              " expects a bf16 channels_last GPU tensor");
+  auto ohw = check_pool_geometry(op, x, l.C, l.N, x.size(2), x.size(3), K, S, P);
+  TORCH_CHECK(bn_relu_pool_eligible(x, K, S, P), op,
+              ": needs N >= 1, C a multiple of 8 that divides 2048, fewer than "
+              "2^31 elements and K*K <= 255; got shape ", x.sizes(), ", K=", K);
+  return ohw;
+}
+
+// -> (p, idx, save_mean, save_rstd). The statistics are those of bn_fwd_train
+// (same pass over x, same finalize, which updates the running statistics);
+// p = maxpool(relu(bn(x))) and idx its (N, OH, OW, C) uint8 tap index, 0xFF
+// where the window's maximum is not positive.
+std::vector<at::Tensor> bn_relu_pool_fwd(at::Tensor x, at::Tensor w,
+                                         at::Tensor b, at::Tensor rm,
+                                         at::Tensor rv, double momentum,
+                                         double eps, long K, long S, long P) {
+  auto ohw = bn_relu_pool_check("bn_relu_pool_fwd", x, K, S, P);
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int OH = (int)ohw.first, OW = (int)ohw.second;
+  bn_check_channel_vec(w, x, C, "weight");
+  bn_check_channel_vec(b, x, C, "bias");
+  bn_check_channel_vec(rm, x, C, "running_mean");
+  bn_check_channel_vec(rv, x, C, "running_var");
+  auto opts = x.options().dtype(at::kFloat);
+  const long HW = (long)H * W, M = (long)N * HW;
+  const BNTier tier = bn_tier(M * C, C, 1, 1);
+  TORCH_CHECK(tier.fast, "bn_relu_pool_fwd: not a fast-path shape");
+  auto ws = bn_workspace(tier, C, opts);
+  auto save_mean = at::empty({C}, opts);
+  auto save_rstd = at::empty({C}, opts);
+  auto p = at::empty({N, C, OH, OW}, x.options(), at::MemoryFormat::ChannelsLast);
+  auto idx = at::empty({N, OH, OW, C}, x.options().dtype(at::kByte));
+  auto s = cur_stream();
+  tfosr_bn_stats(x.data_ptr(), 1, 1, ws.data_ptr<float>(), tier.nb, N, C, HW, s);
+  tfosr_bn_finalize(ws.data_ptr<float>(), tier.nb, x.data_ptr(), 1, 1, HW,
+                    save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),
+                    rm.data_ptr<float>(), rv.data_ptr<float>(), M, C,
+                    (float)momentum, (float)eps, s);
+  tfosr_bn_relu_pool_fwd(x.data_ptr(), p.data_ptr(),
+                         idx.data_ptr<unsigned char>(),
+                         save_mean.data_ptr<float>(),
+                         save_rstd.data_ptr<float>(), w.data_ptr<float>(),
+                         b.data_ptr<float>(), N, C, H, W, OH, OW, (int)K,
+                         (int)S, (int)P, s);
+  return {p, idx, save_mean, save_rstd};
+}
+
+// -> (dx, dgamma, dbeta) from the conv output x, the pooled gradient dp and
+// the idx bn_relu_pool_fwd returned
+std::vector<at::Tensor> bn_relu_pool_bwd(at::Tensor x, at::Tensor dp,
+                                         at::Tensor idx, at::Tensor w,
+                                         at::Tensor save_mean,
+                                         at::Tensor save_rstd, long K, long S,
+                                         long P) {
+  auto ohw = bn_relu_pool_check("bn_relu_pool_bwd", x, K, S, P);
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int OH = (int)ohw.first, OW = (int)ohw.second;
+  TORCH_CHECK(dp.device() == x.device() && dp.scalar_type() == at::kBFloat16 &&
+                  dp.dim() == 4 && dp.size(0) == N && dp.size(1) == C &&
+                  dp.size(2) == OH && dp.size(3) == OW,
+              "bn_relu_pool_bwd: dp must be the bf16 (", N, ", ", C, ", ", OH,
+              ", ", OW, ") gradient on the input's device");
+  TORCH_CHECK(idx.scalar_type() == at::kByte && idx.is_contiguous() &&
+                  idx.device() == x.device() && idx.dim() == 4 &&
+                  idx.size(0) == N && idx.size(1) == OH && idx.size(2) == OW &&
+                  idx.size(3) == C,
+              "bn_relu_pool_bwd: idx must be the contiguous uint8 (N, OH, OW, "
+              "C) tensor bn_relu_pool_fwd returned, on the input's device");
+  bn_check_channel_vec(w, x, C, "weight");
+  bn_check_channel_vec(save_mean, x, C, "save_mean");
+  bn_check_channel_vec(save_rstd, x, C, "save_rstd");
+  dp = dp.contiguous(at::MemoryFormat::ChannelsLast);
+  auto opts = x.options().dtype(at::kFloat);
+  const int nb = tfosr_bn_pool_blocks((long)N * OH * OW * C);
+  auto ws = at::empty({(long)nb * 2 * C}, opts);
+  auto dg = at::empty({C}, opts);
+  auto db = at::empty({C}, opts);
+  auto dx = at::empty_like(x);
+  auto s = cur_stream();
+  tfosr_bn_relu_pool_bwd_stats(x.data_ptr(), dp.data_ptr(),
+                               idx.data_ptr<unsigned char>(),
+                               save_mean.data_ptr<float>(),
+                               save_rstd.data_ptr<float>(),
+                               ws.data_ptr<float>(), nb, N, C, H, W, OH, OW,
+                               (int)K, (int)S, (int)P, s);
+  tfosr_bn_bwd_merge(ws.data_ptr<float>(), nb, dg.data_ptr<float>(),
+                     db.data_ptr<float>(), C, s);
+  tfosr_bn_relu_pool_bwd_dx(x.data_ptr(), dp.data_ptr(),
+                            idx.data_ptr<unsigned char>(), dx.data_ptr(),
+                            save_mean.data_ptr<float>(),
+                            save_rstd.data_ptr<float>(), w.data_ptr<float>(),
+                            dg.data_ptr<float>(), db.data_ptr<float>(), N, C,
+                            H, W, OH, OW, (int)K, (int)S, (int)P, s);
+  return {dx, dg, db};
+}
+
+// One launch of one kernel of csrc/bn_pool.hip on caller-owned tensors, for
+// tools/bn_bench.py --stempool (the two entries above run three launches
+// each). family: 0 forward (x -> pooled, idx; mean, rstd, weight, bias),
+// 1 bwd stats (x, pooled = dp, idx -> ws of bn_relu_pool_blocks * 2C floats;
+// mean, rstd), 2 bwd dx (x, pooled = dp, idx -> out; mean, rstd, weight,
+// dgamma, dbeta).
+void bn_relu_pool_stage(int family, at::Tensor x, at::Tensor pooled,
+                        at::Tensor idx, c10::optional<at::Tensor> out,
+                        c10::optional<at::Tensor> ws, std::vector<at::Tensor> p,
+                        long K, long S, long P) {
+  auto ohw = bn_relu_pool_check("bn_relu_pool_stage", x, K, S, P);
+  const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int OH = (int)ohw.first, OW = (int)ohw.second;
+  const size_t need[3] = {4, 2, 5};
+  TORCH_CHECK(family >= 0 && family < 3, "bn_relu_pool_stage: family 0..2");
+  TORCH_CHECK(p.size() == need[family], "bn_relu_pool_stage: family ", family,
+              " takes ", need[family], " per-channel vectors");
+  for (auto& t : p) bn_check_channel_vec(t, x, C, "per-channel vector");
+  TORCH_CHECK(pooled.device() == x.device() &&
+                  pooled.scalar_type() == at::kBFloat16 && pooled.dim() == 4 &&
+                  pooled.size(0) == N && pooled.size(1) == C &&
+                  pooled.size(2) == OH && pooled.size(3) == OW &&
+                  pooled.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "bn_relu_pool_stage: pooled must be bf16 channels_last (N, C, "
+              "OH, OW) on the input's device");
+  TORCH_CHECK(idx.scalar_type() == at::kByte && idx.is_contiguous() &&
+                  idx.device() == x.device() &&
+                  idx.numel() == pooled.numel(),
+              "bn_relu_pool_stage: idx must hold N*OH*OW*C contiguous bytes");
+  const int nb = tfosr_bn_pool_blocks(pooled.numel());
+  if (family == 1)
+    TORCH_CHECK(ws.has_value() && ws->device() == x.device() &&
+                    ws->scalar_type() == at::kFloat && ws->is_contiguous() &&
+                    ws->numel() >= (long)nb * 2 * C,
+                "bn_relu_pool_stage: ws must hold nb * 2C floats");
+  if (family == 2) {
+    TORCH_CHECK(out.has_value(), "bn_relu_pool_stage: out is required");
+    bn_check_like(*out, x, true, true, "out");
+  }
+  auto f = [&](size_t i) { return p[i].data_ptr<float>(); };
+  auto s = cur_stream();
+  unsigned char* ip = idx.data_ptr<unsigned char>();
+  switch (family) {
+    case 0:
+      tfosr_bn_relu_pool_fwd(x.data_ptr(), pooled.data_ptr(), ip, f(0), f(1),
+                             f(2), f(3), N, C, H, W, OH, OW, (int)K, (int)S,
+                             (int)P, s);
+      break;
+    case 1:
+      tfosr_bn_relu_pool_bwd_stats(x.data_ptr(), pooled.data_ptr(), ip, f(0),
+                                   f(1), ws->data_ptr<float>(), nb, N, C, H, W,
+                                   OH, OW, (int)K, (int)S, (int)P, s);
+      break;
+    default:
+      tfosr_bn_relu_pool_bwd_dx(x.data_ptr(), pooled.data_ptr(), ip,
+                                out->data_ptr(), f(0), f(1), f(2), f(3), f(4),
+                                N, C, H, W, OH, OW, (int)K, (int)S, (int)P, s);
+  }
+}
+
 void sgd_step(at::Tensor p, at::Tensor g, at::Tensor m, double lr, double mu,
               double wd, bool nesterov) {
   check_flat_state("sgd_step", p, {&g, &m});
@@ -1167,7 +1358,7 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 12
+#define TFOSR_API_VERSION 13
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
@@ -2028,6 +2219,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_fwd_train", &bn_fwd_train);
   m.def("bn_fwd_eval", &bn_fwd_eval);
   m.def("bn_bwd", &bn_bwd);
+  m.def("bn_relu_pool_eligible", &bn_relu_pool_eligible, py::arg("x"),
+        py::arg("K"), py::arg("S"), py::arg("P"));
+  m.def("bn_relu_pool_fwd", &bn_relu_pool_fwd);
+  m.def("bn_relu_pool_bwd", &bn_relu_pool_bwd);
+  m.def("bn_relu_pool_stage", &bn_relu_pool_stage);
+  m.def("bn_relu_pool_blocks", [](long pooled_numel) {
+    TORCH_CHECK(pooled_numel >= 0, "bn_relu_pool_blocks: negative size");
+    return tfosr_bn_pool_blocks(pooled_numel);
+  });
   m.def("bn_dual_eligible", &bn_dual_eligible);
   m.def("bn_dual_fwd_train", &bn_dual_fwd_train);
   m.def("bn_dual_bwd", &bn_dual_bwd);

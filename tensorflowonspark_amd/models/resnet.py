@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from ..ops.modules import (Conv1x1, Conv3x3, FusedBN, FusedBNAddReLU,
-                           FusedBNReLU, FusedMaxPool2d, StemConv7x7)
+                           FusedBNReLU, FusedMaxPool2d, StemConv7x7,
+                           stem_forward)
 
 
 @torch.jit.ignore
@@ -26,6 +27,13 @@ def _maybe_pack_weights(model, x) -> None:
     if x.is_cuda and x.dtype == torch.bfloat16 and model.training:
         from ..ops.packplan import ensure_packed
         ensure_packed(model, x)
+
+
+@torch.jit.ignore
+def _stem_forward(model, x) -> torch.Tensor:
+    # model.stem(x), with BatchNorm + ReLU + max-pool as one op where the stem
+    # is the ImageNet one in training on the GPU (TFOS_STEM_POOL)
+    return stem_forward(model.stem, x)
 
 
 def conv3x3(cin, cout, stride=1):
@@ -240,9 +248,11 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        if not torch.jit.is_scripting():
+        if torch.jit.is_scripting():
+            x = self.stem(x)
+        else:
             _maybe_pack_weights(self, x)
-        x = self.stem(x)
+            x = _stem_forward(self, x)
         x = self.stages(x)
         x = self.avgpool(x)
         x = torch.flatten(x, 1)

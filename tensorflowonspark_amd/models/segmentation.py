@@ -19,7 +19,8 @@ from ..ops.modules import (BilinearUpsample, ConvTranspose2dHead,
                            ConvTranspose2dMFMA, DepthwiseConv3x3,
                            DilatedConv3x3, FusedBN, FusedBNAdd, FusedBNReLU,
                            PointwiseConv)
-from .resnet import Bottleneck, ResNet, _maybe_pack_weights
+from .resnet import (Bottleneck, ResNet, _maybe_pack_weights,
+                     _stem_forward)
 
 
 class ConvBNReLU(nn.Sequential):
@@ -230,9 +231,11 @@ class DilatedResNet50(ResNet):
         del self.avgpool
 
     def forward(self, x):
-        if not torch.jit.is_scripting():
+        if torch.jit.is_scripting():
+            x = self.stem(x)
+        else:
             _maybe_pack_weights(self, x)
-        x = self.stem(x)
+            x = _stem_forward(self, x)
         return self.stages(x)
 
 

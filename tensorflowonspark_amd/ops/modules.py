@@ -2141,6 +2141,72 @@ class StemConv7x7(nn.Module):
 
 
 # ---------------------------------------------------------------------------
+# ResNet stem tail: BatchNorm + ReLU + max-pool as one op (csrc/bn_pool.hip)
+# ---------------------------------------------------------------------------
+
+class _BNReLUPoolFn(torch.autograd.Function):
+    """p = maxpool(relu(bn(x))) in training. Saves the conv output x and one
+    index byte per pooled element: neither relu(bn(x)) nor a sign mask is
+    written, and the pool's input gradient never exists as a tensor."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum,
+                eps, k, s, p):
+        ext = get_ext(required=True)
+        out, idx, save_mean, save_rstd = ext.bn_relu_pool_fwd(
+            x, weight, bias, running_mean, running_var, momentum, eps, k, s, p)
+        ctx.save_for_backward(x, idx, weight, save_mean, save_rstd)
+        ctx.pool = (k, s, p)
+        return out
+
+    @staticmethod
+    def backward(ctx, dp):
+        ext = get_ext(required=True)
+        x, idx, weight, save_mean, save_rstd = ctx.saved_tensors
+        dx, dweight, dbias = ext.bn_relu_pool_bwd(
+            x, dp, idx, weight, save_mean, save_rstd, *ctx.pool)
+        return (dx, dweight, dbias) + (None,) * 7
+
+
+def _stem_pool_mode():
+    """TFOS_STEM_POOL, read at call time: 'on' (default) fuses the stem's
+    BatchNorm + ReLU + max-pool where the shape is eligible, 'off' runs the
+    three modules one after the other."""
+    mode = os.environ.get("TFOS_STEM_POOL", "on")
+    if mode not in ("on", "off"):
+        raise ValueError("TFOS_STEM_POOL must be on or off, got "
+                         "{!r}".format(mode))
+    return mode
+
+
+def stem_forward(stem, x):
+    """``stem(x)`` for a ResNet stem. In training on a bf16 channels_last GPU
+    tensor, a stem that is exactly (StemConv7x7, FusedBNReLU, FusedMaxPool2d)
+    runs its conv unchanged and then the fused BatchNorm + ReLU + max-pool
+    (TFOS_STEM_POOL=on, the default, and a shape the kernels take); every
+    other case is ``stem(x)`` itself."""
+    fuse = _stem_pool_mode() == "on"
+    if not (fuse and x.is_cuda and x.dtype == torch.bfloat16
+            and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last)
+            and len(stem) == 3 and type(stem[0]) is StemConv7x7
+            and type(stem[1]) is FusedBNReLU
+            and type(stem[2]) is FusedMaxPool2d and stem[1].training):
+        return stem(x)
+    ext = get_ext(required=True)
+    if ext is None:
+        return stem(x)
+    conv, bn, pool = stem[0], stem[1], stem[2]
+    y = conv(x)
+    if not ext.bn_relu_pool_eligible(y, pool.k, pool.s, pool.p):
+        return pool(bn(y))
+    bn.num_batches_tracked += 1
+    return _BNReLUPoolFn.apply(y, bn.weight, bn.bias, bn.running_mean,
+                               bn.running_var, bn.momentum, bn.eps, pool.k,
+                               pool.s, pool.p)
+
+
+# ---------------------------------------------------------------------------
 # TorchScript export support: every fused/MFMA module (and the blocks built
 # from them) swaps to an equivalent plain-op module at scripting time, so
 # TFNode.export_saved_model produces a loadable TorchScript model for ANY

@@ -31,6 +31,9 @@ is what the ``TFOS_BN_EPI=auto`` rule in ops/modules.py was read off.
 whose width takes the NHWC row tier, each kernel family with ``TFOS_BN_ROWS``
 on against off (the generic kernels), see ``rows_main``.
 
+``--stempool`` is a fourth: the stem's BatchNorm + ReLU + max-pool as three ops
+against the fused kernels of csrc/bn_pool.hip, see ``stempool_main``.
+
 The variants timed are the ones the ResNet-50 step runs most: stats; apply
 with ReLU (and with ReLU + residual, ``apply+res``); bwd stats with the mask
 (and writing the gated gradient, ``bwd stats+g``); bwd dx with the mask.
@@ -336,6 +339,143 @@ def rows_main(args):
             json.dump(records, f, indent=1)
 
 
+# --stempool shapes: the ResNet-50 stem at b1024 and DeepLabV3's at b32
+STEM_SHAPES = [(1024, 64, 112, 112), (32, 64, 256, 256)]
+
+
+def stempool_main(args):
+    """--stempool: the stem tail BatchNorm + ReLU + max-pool (3/2/1) as three
+    ops against the fused entries of csrc/bn_pool.hip, on the two stem shapes,
+    alternating in one process: every row of a shape is timed once per round,
+    one after the other. Rows: a plain device copy of the conv output (the
+    yardstick), each kernel alone (old: apply, maxpool fwd, maxpool bwd, bwd
+    stats, bwd dx; new: fwd, bwd stats, bwd dx) with the bytes it must move
+    over its time, and the chains as the autograd functions run them (fwd and
+    fwd + bwd). Then the two acceptance comparisons, each with its margin
+    against the larger of the two spreads (max - min over the rounds)."""
+    from tensorflowonspark_amd.ops import get_ext
+    ext = get_ext(required=True)
+    dev, bf = "cuda", torch.bfloat16
+    K, S, P = 3, 2, 1
+    records = []
+    print("stem tail, bf16: ms per launch, median / spread of {} rounds x {} "
+          "launches".format(args.rounds, args.iters))
+    for N, C, H, W in STEM_SHAPES:
+        OH, OW = (H + 2 * P - K) // S + 1, (W + 2 * P - K) // S + 1
+        shape = (N, C, H, W)
+
+        def act(s):
+            return torch.randn(s, device=dev).to(bf).contiguous(
+                memory_format=torch.channels_last)
+
+        x, out = act(shape), act(shape)
+        dp = act((N, C, OH, OW))
+        w = torch.rand(C, device=dev) + 0.5
+        b = torch.randn(C, device=dev) * 0.1
+        rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
+        # one real forward of each path: y, mask, idx as training has them
+        y, mean, rstd, mask = ext.bn_fwd_train(x, None, w, b, rm, rv, 0.1,
+                                               1e-5, True)
+        p_old, idx_old = ext.maxpool_fwd(y, K, S, P)
+        p_new, idx_new, _, _ = ext.bn_relu_pool_fwd(x, w, b, rm, rv, 0.1,
+                                                    1e-5, K, S, P)
+        dy = ext.maxpool_bwd(dp, idx_old, H, W, K, S, P)
+        _, dg, db = ext.bn_bwd(x, dy, y, mask, w, mean, rstd, True, False)
+        nb_old = ext.bn_fast_blocks(x.numel(), C, True, True)
+        nb_new = ext.bn_relu_pool_blocks(dp.numel())
+        ws = torch.empty(max(nb_old, nb_new) * 2 * C, device=dev)
+        t, tp = x.numel() * 2, dp.numel() * 2       # bytes: x-sized, pooled
+        ti, tm = dp.numel(), x.numel() // 8          # index bytes, mask bytes
+        st, ps = ext.bn_stage, ext.bn_relu_pool_stage
+        v4, v2 = [mean, rstd, w, b], [mean, rstd]
+        v5 = [mean, rstd, w, dg, db]
+
+        def old_fwd():
+            yy = ext.bn_fwd_train(x, None, w, b, rm, rv, 0.1, 1e-5, True)
+            return yy, ext.maxpool_fwd(yy[0], K, S, P)
+
+        def new_fwd():
+            return ext.bn_relu_pool_fwd(x, w, b, rm, rv, 0.1, 1e-5, K, S, P)
+
+        def old_both():
+            yy, (_, ii) = old_fwd()
+            d = ext.maxpool_bwd(dp, ii, H, W, K, S, P)
+            ext.bn_bwd(x, d, yy[0], yy[3], w, yy[1], yy[2], True, False)
+
+        def new_both():
+            _, ii, m, r = new_fwd()
+            ext.bn_relu_pool_bwd(x, dp, ii, w, m, r, K, S, P)
+
+        rows = [
+            ("(copy)", 2 * t, lambda: out.copy_(x)),
+            ("stats (both)", t, lambda: st(0, x, None, None, None, ws, [],
+                                           False, None)),
+            ("old apply", 2 * t + tm,
+             lambda: st(1, x, None, out, mask, ws, v4, True, None)),
+            ("old maxpool fwd", t + tp + ti,
+             lambda: ext.maxpool_fwd(y, K, S, P)),
+            ("new fwd", t + tp + ti,
+             lambda: ps(0, x, p_new, idx_new, None, None, v4, K, S, P)),
+            ("old maxpool bwd", tp + ti + t,
+             lambda: ext.maxpool_bwd(dp, idx_old, H, W, K, S, P)),
+            ("old bwd stats", 2 * t + tm,
+             lambda: st(2, x, dy, None, mask, ws, v2, True, None)),
+            ("old bwd dx", 3 * t + tm,
+             lambda: st(3, x, dy, out, mask, ws, v5, True, None)),
+            ("new bwd stats", t + tp + ti,
+             lambda: ps(1, x, dp, idx_new, None, ws, v2, K, S, P)),
+            ("new bwd dx", 2 * t + tp + ti,
+             lambda: ps(2, x, dp, idx_new, out, None, v5, K, S, P)),
+            ("old chain fwd", None, old_fwd),
+            ("new chain fwd", None, new_fwd),
+            ("old chain fwd+bwd", None, old_both),
+            ("new chain fwd+bwd", None, new_both),
+        ]
+        for _, _, fn in rows:
+            fn()
+        torch.cuda.synchronize()
+        ms = {n: [] for n, _, _ in rows}
+        for _ in range(args.rounds):
+            for n, _, fn in rows:
+                ms[n].append(time_round(fn, args.iters))
+        med = {n: statistics.median(v) for n, v in ms.items()}
+        spr = {n: max(v) - min(v) for n, v in ms.items()}
+        print("{}x{}x{}x{} ({:.0f} MB)".format(N, C, H, W, t / 1e6))
+        print("  {:<18s} {:>8s} {:>8s} {:>8s} {:>7s}".format(
+            "row", "ms", "spread", "GB", "TB/s"))
+        for n, nbytes, _ in rows:
+            if nbytes is None:
+                print("  {:<18s} {:8.4f} {:8.4f}".format(n, med[n], spr[n]))
+            else:
+                print("  {:<18s} {:8.4f} {:8.4f} {:8.3f} {:7.2f}".format(
+                    n, med[n], spr[n], nbytes / 1e9, nbytes / med[n] / 1e9))
+            records.append({"shape": shape, "row": n, "bytes": nbytes,
+                            "ms": ms[n]})
+
+        def verdict(what, old_names, new_names):
+            o = sum(med[n] for n in old_names)
+            nw = sum(med[n] for n in new_names)
+            sp = max(sum(spr[n] for n in old_names),
+                     sum(spr[n] for n in new_names))
+            ok = o - nw > sp
+            print("  {}: old {:.4f} new {:.4f} margin {:+.4f} spread {:.4f} "
+                  "-> {}".format(what, o, nw, o - nw, sp,
+                                 "ahead" if ok else "NOT ahead"), flush=True)
+
+        verdict("fwd kernel vs maxpool fwd alone", ["old maxpool fwd"],
+                ["new fwd"])
+        verdict("bwd pair vs maxpool bwd + bwd dx",
+                ["old maxpool bwd", "old bwd dx"],
+                ["new bwd stats", "new bwd dx"])
+        verdict("chain fwd", ["old chain fwd"], ["new chain fwd"])
+        verdict("chain fwd+bwd", ["old chain fwd+bwd"], ["new chain fwd+bwd"])
+        del x, out, dp, y, dy, mask, p_old, p_new, idx_old, idx_new, rows
+        torch.cuda.empty_cache()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(records, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -349,11 +489,17 @@ def main():
                          "conv epilogue vs the separate pass")
     ap.add_argument("--rows", action="store_true",
                     help="per U-Net row-tier BatchNorm: TFOS_BN_ROWS on vs off")
+    ap.add_argument("--stempool", action="store_true",
+                    help="the stem's BatchNorm + ReLU + max-pool: three ops vs "
+                         "the fused entries")
     ap.add_argument("--json", metavar="PATH",
-                    help="with --rows: also write every round's times here")
+                    help="with --rows or --stempool: also write every round's "
+                         "times here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bn_bench needs a GPU")
+    if args.stempool:
+        return stempool_main(args)
     if args.rows:
         return rows_main(args)
     if args.epilogue:
