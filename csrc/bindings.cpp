@@ -99,6 +99,10 @@ void tfosr_convt_head_dgrad(const void*, const float*, void*, int, int, int,
                             int, int, hipStream_t);
 void tfosr_convt_head_wrw(const void*, const void*, float*, float*, float*,
                           int, int, int, int, int, hipStream_t);
+int tfosr_convt_wrw_plan(long, int, int, int, int, int*, int*, int*, int*, int*,
+                         long*, int*);
+hipError_t tfosr_convt_wrw(const void*, const void*, float*, float*, long, int,
+                           int, int, int, long, long, hipStream_t);
 void tfosr_pwconv_info(int*, int*, int*);
 void tfosr_pwconv_plan(long, int, int, int*, long*, int*, int*, int*, int*);
 hipError_t tfosr_pwconv_gemm(const void*, const void*, int, void*, long, int,
@@ -1358,7 +1362,7 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 13
+#define TFOSR_API_VERSION 14
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
@@ -1992,6 +1996,103 @@ static std::tuple<at::Tensor, at::Tensor> convt_head_wrw(at::Tensor dy,
 }
 
 // ---------------------------------------------------------------------------
+// Transposed-conv weight gradient (csrc/convt_wrw.hip): k4 s2 p1,
+// output_padding 0, channel counts that are multiples of 8, bf16 channels_last
+// ---------------------------------------------------------------------------
+
+// x or dy as the kernel takes it: the cv_check_act conditions, except that a
+// pixel may be wider than C (a channel slice of a channels_last tensor keeps
+// its parent's pixel stride). Returns the pixel stride in elements.
+static long ctw_check_act(const char* op, const char* name,
+                          const at::Tensor& t) {
+  const long C = t.size(1), H = t.size(2), W = t.size(3);
+  long ps = C;
+  if (!t.is_contiguous(at::MemoryFormat::ChannelsLast)) {
+    ps = t.stride(3);
+    TORCH_CHECK(t.stride(1) == 1 && ps >= C && ps % 8 == 0 &&
+                    t.stride(2) == W * ps && t.stride(0) == H * W * ps,
+                op, ": ", name, " must be channels_last-contiguous, or a "
+                "channel slice of such a tensor with a pixel stride that is a "
+                "multiple of 8; got sizes ", t.sizes(), " strides ",
+                t.strides());
+  }
+  for (int d = 0; d < 4; ++d)
+    TORCH_CHECK(t.size(d) <= INT_MAX, op, ": ", name, " has size ", t.size(d),
+                " in dimension ", d, ", expected at most ", INT_MAX);
+  TORCH_CHECK(C % 8 == 0, op, ": ", name, " must have a multiple of 8 "
+              "channels, got ", C);
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+              " must be 16-byte aligned");
+  return ps;
+}
+
+static py::dict convt_wrw_plan(long N, long H, long W, long Cin, long Cout) {
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && N * H <= INT_MAX && 2 * H <= INT_MAX &&
+                  2 * W <= INT_MAX,
+              "convt_wrw_plan: N, H and W must be positive, with N*H, 2H and "
+              "2W at most ", INT_MAX);
+  TORCH_CHECK(Cin > 0 && Cout > 0 && Cin % 8 == 0 && Cout % 8 == 0 &&
+                  Cin <= INT_MAX && Cout <= INT_MAX &&
+                  Cin * Cout <= INT_MAX / 16,
+              "convt_wrw_plan: Cin and Cout must be positive multiples of 8 "
+              "with Cin*Cout*16 at most ", INT_MAX);
+  int rb = 0, rows = 0, slabs = 0, tiles = 0, grid = 0, lds = 0;
+  long ws = 0;
+  const int ok = tfosr_convt_wrw_plan(N, (int)H, (int)W, (int)Cin, (int)Cout,
+                                      &rb, &rows, &slabs, &tiles, &grid, &ws,
+                                      &lds);
+  py::dict d;
+  d["eligible"] = (bool)ok;
+  d["block_rows"] = rb;
+  d["slab_rows"] = rows;
+  d["slabs"] = slabs;
+  d["tiles"] = tiles;
+  d["grid"] = grid;
+  d["ws_bytes"] = ws;
+  d["lds_bytes"] = lds;
+  return d;
+}
+
+static at::Tensor convt_wrw(at::Tensor dy, at::Tensor x) {
+  const char* op = "convt_wrw";
+  const at::Tensor* ts[2] = {&dy, &x};
+  const char* names[2] = {"dy", "x"};
+  for (int i = 0; i < 2; ++i) {
+    TORCH_CHECK(ts[i]->is_cuda(), op, ": ", names[i],
+                " must be a GPU tensor");
+    TORCH_CHECK(ts[i]->dim() == 4, op, ": ", names[i],
+                " must be 4-D (N, C, H, W), got ", ts[i]->dim(), "-D");
+    TORCH_CHECK(ts[i]->scalar_type() == at::kBFloat16, op, ": ", names[i],
+                " must be bf16, got ", ts[i]->scalar_type());
+  }
+  cv_check_device(op, "x", x, dy);
+  const long N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  const long Cout = dy.size(1);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == 2 * H && dy.size(3) == 2 * W,
+              op, ": x ", x.sizes(), " gives a gradient of [", N, ", Cout, ",
+              2 * H, ", ", 2 * W, "], got ", dy.sizes());
+  auto opts = x.options().dtype(at::kFloat);
+  if (x.numel() == 0 || dy.numel() == 0)
+    return at::zeros({Cin, Cout, 4, 4}, opts);
+  const long dps = ctw_check_act(op, "dy", dy);
+  const long xps = ctw_check_act(op, "x", x);
+  const py::dict plan = convt_wrw_plan(N, H, W, Cin, Cout);
+  TORCH_CHECK(plan["eligible"].cast<bool>(), op, ": W=", W,
+              " is wider than one staged row block holds");
+  const long wsb = plan["ws_bytes"].cast<long>();
+  auto dw = at::empty({Cin, Cout, 4, 4}, opts);
+  at::Tensor ws;
+  if (wsb > 0) ws = at::empty({wsb / 4}, opts);
+  const hipError_t err = tfosr_convt_wrw(
+      x.data_ptr(), dy.data_ptr(), wsb > 0 ? ws.data_ptr<float>() : nullptr,
+      dw.data_ptr<float>(), N, (int)H, (int)W, (int)Cin, (int)Cout, xps, dps,
+      cur_stream());
+  TORCH_CHECK(err == hipSuccess, op, ": launch failed: ",
+              hipGetErrorString(err));
+  return dw;
+}
+
+// ---------------------------------------------------------------------------
 // Pointwise convs (csrc/pwconv.hip): 1x1, stride 1, no bias, channel counts
 // that are multiples of 8 in [8, 960], bf16 channels_last; the weight is the
 // module's contiguous [Cout, Cin, 1, 1] parameter, fp32 or bf16
@@ -2459,6 +2560,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     d["slab"] = slab;
     return d;
   }, py::arg("M"), py::arg("Cin"), py::arg("Cout"));
+
+  m.def("convt_wrw", &convt_wrw, py::arg("dy"), py::arg("x"));
+  m.def("convt_wrw_plan", &convt_wrw_plan, py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("Cin"), py::arg("Cout"));
 
   m.def("pwconv_fwd", &pwconv_fwd, py::arg("x"), py::arg("w"));
   m.def("pwconv_dgrad", &pwconv_dgrad, py::arg("dy"), py::arg("w"));

@@ -89,6 +89,50 @@ def _lib_conv_backward(dy, x, weight, stride, pad, fd, transposed, mask):
     return gx, gw
 
 
+def _ctw_table():
+    """(Cin, Cout, H, W, smallest N) per U-Net up-stack class where
+    tools/convt_wrw_bench.py measured csrc/convt_wrw.hip no slower than the
+    library's weight gradient on the MI355X at that batch and at every larger
+    measured one (docs/performance.md "Transposed-conv weight gradient"; the
+    run is profiles/convt_wrw_bench.json). up1 and up3 won at b64 (1.28x,
+    1.09x) and lost at b1024, which a smallest-N row cannot say: they stay
+    on the library, as does up4, which lost at both."""
+    return (
+        (608, 256, 8, 8, 1024),    # up2: 0.875 ms against 2.05 ms at b1024
+    )
+
+
+def _ctw_auto(N, cin, cout, H, W):
+    """TFOS_CONVT_WRW=auto: in-tree only for a measured class, matched
+    exactly, at a batch of at least its smallest measured winning one. No
+    nearest-shape rule: what was not measured stays on the library."""
+    return any(row[:4] == (cin, cout, H, W) and N >= row[4]
+               for row in _ctw_table())
+
+
+def _ctw_route(x, dy_hw, cin, cout, k, stride, pad):
+    """Does TFOS_CONVT_WRW (read here, at call time) send the weight gradient
+    of this ConvTranspose2d to convt_wrw? x: the layer's input; dy_hw: the
+    output's (H, W), which is (2H, 2W) exactly when output_padding is 0.
+    TFOS_WRW has no say in it."""
+    mode = os.environ.get("TFOS_CONVT_WRW", "auto")
+    if mode == "miopen":
+        return False
+    if mode not in ("hip", "auto"):
+        raise ValueError("TFOS_CONVT_WRW must be auto, hip or miopen, got "
+                         + repr(mode))
+    N, _, H, W = x.shape
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.numel() > 0
+            and (k, stride, pad) == (4, 2, 1)
+            and tuple(dy_hw) == (2 * H, 2 * W)
+            and cin % 8 == 0 and cout % 8 == 0):
+        return False
+    if mode == "auto" and not _ctw_auto(N, cin, cout, H, W):
+        return False
+    return bool(get_ext(required=True).convt_wrw_plan(
+        N, H, W, cin, cout)["eligible"])
+
+
 def _weight_grad(dy, x, weight, k, stride, pad, fd=1, transposed=False,
                  round1=True):
     """dW of a k x k conv (filter dilation fd; ``transposed``: of a
@@ -103,7 +147,12 @@ def _weight_grad(dy, x, weight, k, stride, pad, fd=1, transposed=False,
                  where the caller passes round1=False
       library    _lib_conv_backward (aten, on a channels_last bf16 weight):
                  everything else (miopen, most of auto), every transposed conv
+                 that TFOS_CONVT_WRW (_ctw_route, asked first) does not send
+                 to convt_wrw
     """
+    if transposed and _ctw_route(x, dy.shape[2:], weight.shape[0],
+                                 weight.shape[1], k, stride, pad):
+        return get_ext(required=True).convt_wrw(dy, x).to(weight.dtype)
     cout, cin = weight.shape[0], weight.shape[1]
     backend = _wrw_backend(os.environ.get("TFOS_WRW", "auto"), k, cin, cout,
                            stride, fd, transposed, round1)
@@ -1314,6 +1363,29 @@ class _ConvT2dFn(torch.autograd.Function):
         return dx, dw, None, None, None
 
 
+class _ConvTLibWrwFn(torch.autograd.Function):
+    """ConvTranspose2d k4 s2 p1 for the layers _ConvT2dFn does not take
+    (channels not multiples of 32, or below its size gate): forward and input
+    gradient are the library's, the weight gradient is convt_wrw."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        return F.conv_transpose2d(x, weight.to(x.dtype), stride=2, padding=1)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = _cl_bf16(dy)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = _lib_conv_backward(dy, x, weight, 2, 1, 1, True,
+                                    (True, False))[0]
+        if ctx.needs_input_grad[1]:
+            dw = get_ext(required=True).convt_wrw(dy, x).to(weight.dtype)
+        return dx, dw
+
+
 class ConvTranspose2dMFMA(nn.Module):
     """Transposed conv routed to the implicit-GEMM MFMA kernel on GPU.
 
@@ -1343,6 +1415,13 @@ class ConvTranspose2dMFMA(nn.Module):
             x = x.contiguous(memory_format=torch.channels_last)
             return _ConvT2dFn.apply(x, self.weight, self.stride, self.padding,
                                     self.output_padding)
+        k = self.weight.shape[2]
+        if x.is_cuda and x.dim() == 4 and self.output_padding == 0 \
+                and self.weight.shape[3] == k and _ctw_route(
+                    x, (2 * x.shape[2], 2 * x.shape[3]), self.weight.shape[0],
+                    self.weight.shape[1], k, self.stride, self.padding):
+            x = x.contiguous(memory_format=torch.channels_last)
+            return _ConvTLibWrwFn.apply(x, self.weight)
         return F.conv_transpose2d(x, self.weight.to(x.dtype),
                                   stride=self.stride, padding=self.padding,
                                   output_padding=self.output_padding)

@@ -20,7 +20,7 @@ OUT_SO = os.path.join(OUT_DIR, "tfosr_hip_ops.so")
 BUILD = os.path.join(REPO, "build", "hip")
 
 SOURCES = ["bn_relu.hip", "softmax_xent_dense.hip", "elementwise.hip",
-           "gemm_mfma.hip", "conv3x3_mfma.hip", "conv3x3_halo.hip", "conv_wrw_mfma.hip", "conv_wrw2.hip", "maxpool.hip", "dwconv3x3.hip", "convt_head.hip",
+           "gemm_mfma.hip", "conv3x3_mfma.hip", "conv3x3_halo.hip", "conv_wrw_mfma.hip", "conv_wrw2.hip", "maxpool.hip", "dwconv3x3.hip", "convt_head.hip", "convt_wrw.hip",
            "upsample_bilinear.hip", "pwconv.hip", "bn_pool.hip",
            "tfrecord_codec.cpp", "bindings.cpp"]
 
