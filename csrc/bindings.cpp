@@ -64,6 +64,10 @@ void tfosr_gemm_bt(const void*, const void*, void*, int, int, int, int,
                    hipStream_t);
 void tfosr_gemm_bt_acc(const void*, const void*, void*, int, int, int, int,
                        int, hipStream_t);
+int tfosr_gemm_bt_gate_eligible(int, int, int);
+void tfosr_gemm_bt_gate(const void*, const void*, const void*,
+                        const unsigned char*, void*, int, int, int,
+                        hipStream_t);
 void tfosr_mfma_probe(const short*, const short*, float*, hipStream_t);
 void tfosr_maxpool_fwd(const void*, void*, unsigned char*, int, int, int, int,
                        int, int, int, int, int, int, hipStream_t);
@@ -1362,7 +1366,7 @@ at::Tensor mfma_probe(at::Tensor a, at::Tensor b) {
 // bump when the binding surface changes: the Python side refuses to run
 // against a stale in-tree .so (clear "rebuild" message instead of a random
 // AttributeError mid-training)
-#define TFOSR_API_VERSION 14
+#define TFOSR_API_VERSION 15
 
 // Largest filter reach fd*(k-1) the conv entries accept. The kernels form
 // ih = oh*S - P + r*fd in int; image coordinates stay below 2^24 in any
@@ -2428,6 +2432,49 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     tfosr_gemm_bt_acc(a.data_ptr(), b.data_ptr(), c.data_ptr(),
                       /*out_bf16=*/1, M, Nn, K, 1, cur_stream());
     return c;
+  });
+  // does gemm_bt_gate take A[M,K] @ B[N,K]^T? (not N % 8 != 0, not a shape
+  // on the 256^2 kernel: the caller keeps gemm_bt_acc there)
+  m.def("gemm_bt_gate_eligible", [](long M, long N, long K) {
+    return M > 0 && M <= INT_MAX && N > 0 && N <= INT_MAX && K > 0 &&
+           K <= INT_MAX && tfosr_gemm_bt_gate_eligible((int)M, (int)N, (int)K);
+  });
+  // dx = A @ B^T + gate(dy, mask): gemm_bt_acc on a c that holds dy where the
+  // ReLU bitmask (one byte per 8 elements, as bn_fwd_train returns it) is set
+  // and +0 elsewhere, bit for bit, without that tensor: dy and mask are only
+  // read, dx is a fresh [M, N] tensor.
+  m.def("gemm_bt_gate", [](at::Tensor a, at::Tensor b, at::Tensor dy,
+                           at::Tensor mask) {
+    TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && dy.dim() == 2,
+                "gemm_bt_gate: A[M,K], B[N,K], dy[M,N] must be 2-D");
+    TORCH_CHECK(a.is_cuda(), "gemm_bt_gate: a must be a GPU tensor");
+    TORCH_CHECK(b.device() == a.device() && dy.device() == a.device() &&
+                    mask.device() == a.device(),
+                "gemm_bt_gate: b, dy and mask must be on ", a.device());
+    TORCH_CHECK(a.is_contiguous() && b.is_contiguous() && dy.is_contiguous() &&
+                    mask.is_contiguous(),
+                "gemm_bt_gate: a, b, dy and mask must be contiguous");
+    TORCH_CHECK(a.scalar_type() == at::kBFloat16 &&
+                    b.scalar_type() == at::kBFloat16 &&
+                    dy.scalar_type() == at::kBFloat16,
+                "gemm_bt_gate: a, b and dy must be bfloat16");
+    long M = a.size(0), K = a.size(1), Nn = b.size(0);
+    TORCH_CHECK(b.size(1) == K && dy.size(0) == M && dy.size(1) == Nn,
+                "gemm_bt_gate: A[M,K], B[N,K], dy[M,N]");
+    TORCH_CHECK(K % 32 == 0, "gemm_bt_gate: K must be a multiple of 32");
+    TORCH_CHECK(Nn % 8 == 0, "gemm_bt_gate: N must be a multiple of 8, one "
+                "mask byte per 8 elements of a row");
+    TORCH_CHECK(mask.scalar_type() == at::kByte && mask.numel() == M * Nn / 8,
+                "gemm_bt_gate: mask must be uint8 with M * N / 8 elements");
+    TORCH_CHECK(M > 0 && M <= INT_MAX && Nn <= INT_MAX && K <= INT_MAX &&
+                    tfosr_gemm_bt_gate_eligible((int)M, (int)Nn, (int)K),
+                "gemm_bt_gate: no gating epilogue for M ", M, ", N ", Nn,
+                ", K ", K, " (gemm_bt_gate_eligible)");
+    auto dx = at::empty({M, Nn}, dy.options());
+    tfosr_gemm_bt_gate(a.data_ptr(), b.data_ptr(), dy.data_ptr(),
+                       mask.data_ptr<unsigned char>(), dx.data_ptr(), (int)M,
+                       (int)Nn, (int)K, cur_stream());
+    return dx;
   });
   m.def("conv_wrw2", &conv_wrw2, py::arg("dy"), py::arg("x"), py::arg("R"),
         py::arg("S_f"), py::arg("stride"), py::arg("P"), py::arg("fd") = 1);

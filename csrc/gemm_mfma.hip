@@ -47,12 +47,24 @@ __device__ __forceinline__ void stage16(const char* src,
 // tile_m / BM of part[ceil(M / BM)][2][N] — see mfma_stats_epilogue.h. The
 // stores themselves are the non-STATS kernel's. Needs K >= BK, so that the K
 // loop's closing barrier has retired every read of the staging ring.
-template <typename OT, int WGM, int WGN, bool ACC = false, bool STATS = false>
+//
+// GATE (bf16 output only): C = A @ B^T + gate(gdy), where gate() keeps element
+// j of the 8-element vector v = (m * N + n) / 8 of gdy[M, N] if bit j of
+// gmask[v] is set and is +0 otherwise: the ReLU bitmask bn_apply_fast writes,
+// one byte per vector. This is ACC on a C that holds the gated gradient, with
+// the same two roundings (bf16(float(bf16(acc)) + float(g))), except that the
+// gated tensor is never materialised: gdy and gmask are only read, C is only
+// written. Needs N % 8 == 0, so that a 16 B chunk is whole or absent.
+template <typename OT, int WGM, int WGN, bool ACC = false, bool STATS = false,
+          bool GATE = false>
 __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
-    OT* __restrict__ C, int M, int N, int K, float* __restrict__ part) {
+    OT* __restrict__ C, int M, int N, int K, float* __restrict__ part,
+    const bf16_t* __restrict__ gdy, const unsigned char* __restrict__ gmask) {
   static_assert(!STATS || (!ACC && std::is_same<OT, bf16_t>::value),
                 "the statistics epilogue exists for plain bf16 stores only");
+  static_assert(!GATE || (!ACC && !STATS && std::is_same<OT, bf16_t>::value),
+                "the gating epilogue exists for plain bf16 stores only");
   constexpr int BM = WGM * 64;
   constexpr int BN = WGN * 64;
   constexpr int ABYTES = BM * BK * 2;  // 64 B per row
@@ -157,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
   // epilogue: C/D layout col = lane&15, row = (lane>>4)*4 + reg
   const int ccol = lane & 15;
   const int crow0 = (lane >> 4) * 4;
-  if constexpr (ACC && std::is_same<OT, bf16_t>::value) {
+  if constexpr ((ACC || GATE) && std::is_same<OT, bf16_t>::value) {
     // shuffle epilogue: the mfma lane layout reads/writes C in scattered
     // 32 B runs — fine for pure stores (write combining) but a read-modify-
     // write at that pattern costs as much as a separate eager add. Stage the
@@ -185,6 +197,26 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
       int row = c >> 3, col0 = (c & 7) * 8;
       long m = tile_m + wr * 64 + row;
       long n = tile_n + wc * 64 + col0;
+      if constexpr (GATE) {
+        if (m >= M || n >= N) continue;
+        s16x8 add = *(AS_LDS(s16x8*))(myl + (row * 64 + col0) * 2);
+        s16x8 g = *(const s16x8*)((const char*)gdy + (m * N + n) * 2);
+        const unsigned bits = gmask[(m * N + n) >> 3];
+        s16x8 out;
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          short sa = add[j], sb = ((bits >> j) & 1) ? g[j] : (short)0;
+          bf16_t a, b;
+          __builtin_memcpy(&a, &sa, 2);
+          __builtin_memcpy(&b, &sb, 2);
+          bf16_t o = (bf16_t)((float)a + (float)b);
+          short so;
+          __builtin_memcpy(&so, &o, 2);
+          out[j] = so;
+        }
+        *(s16x8*)((char*)C + (m * N + n) * 2) = out;
+        continue;
+      }
       if (m >= M || n + 7 >= N) {     // slow scalar tail at ragged edges
         if (m < M)
           for (int j = 0; j < 8 && n + j < N; ++j) {
@@ -426,13 +458,13 @@ void tfosr_gemm_bt_stats(const void* A, const void* B, void* C, float* part,
     dim3 grid(((M + 255) / 256) * ((N + 63) / 64));
     hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 4, 1, false, true>), grid,
                        dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)B,
-                       (bf16_t*)C, M, N, K, part);
+                       (bf16_t*)C, M, N, K, part, nullptr, nullptr);
     return;
   }
   dim3 grid(((M + 127) / 128) * ((N + 127) / 128));
   hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 2, 2, false, true>), grid,
                      dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)B,
-                     (bf16_t*)C, M, N, K, part);
+                     (bf16_t*)C, M, N, K, part, nullptr, nullptr);
 }
 
 void tfosr_gemm_bt(const void* A, const void* B, void* C, int out_bf16,
@@ -474,15 +506,17 @@ void tfosr_gemm_bt_acc(const void* A, const void* B, void* C, int out_bf16,
       if (accum)
         hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 4, 1, true>), grid,
                            dim3(256), 0, s, (const bf16_t*)A,
-                           (const bf16_t*)B, (bf16_t*)C, M, N, K, nullptr);
+                           (const bf16_t*)B, (bf16_t*)C, M, N, K, nullptr,
+                           nullptr, nullptr);
       else
         hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 4, 1, false>), grid,
                            dim3(256), 0, s, (const bf16_t*)A,
-                           (const bf16_t*)B, (bf16_t*)C, M, N, K, nullptr);
+                           (const bf16_t*)B, (bf16_t*)C, M, N, K, nullptr,
+                           nullptr, nullptr);
     } else {
       hipLaunchKernelGGL((gemm_bt_kernel<float, 4, 1>), grid, dim3(256), 0, s,
                          (const bf16_t*)A, (const bf16_t*)B, (float*)C, M, N,
-                         K, nullptr);
+                         K, nullptr, nullptr, nullptr);
     }
     return;
   }
@@ -492,15 +526,45 @@ void tfosr_gemm_bt_acc(const void* A, const void* B, void* C, int out_bf16,
     if (accum)
       hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 2, 2, true>), grid, dim3(256),
                          0, s, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C,
-                         M, N, K, nullptr);
+                         M, N, K, nullptr, nullptr, nullptr);
     else
       hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 2, 2, false>), grid,
                          dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)B,
-                         (bf16_t*)C, M, N, K, nullptr);
+                         (bf16_t*)C, M, N, K, nullptr, nullptr, nullptr);
   } else {
     hipLaunchKernelGGL((gemm_bt_kernel<float, 2, 2>), grid, dim3(256), 0, s,
-                       (const bf16_t*)A, (const bf16_t*)B, (float*)C, M, N, K, nullptr);
+                       (const bf16_t*)A, (const bf16_t*)B, (float*)C, M, N, K,
+                       nullptr, nullptr, nullptr);
   }
+}
+
+// Does tfosr_gemm_bt_gate() take this shape? Not a shape that the dispatch
+// above sends to gemm_bt256_kernel, whose scattered epilogue has no gating
+// variant (K >= 1024: no 1x1 dgrad of a residual block gets there), and not
+// N % 8 != 0, where a mask byte would straddle rows. The caller then keeps
+// bn_bwd's gated-gradient tensor and tfosr_gemm_bt_acc().
+int tfosr_gemm_bt_gate_eligible(int M, int N, int K) {
+  return N % 8 == 0 && K % BK == 0 && K >= BK && !gemm_route256(M, N, K);
+}
+
+// bf16 C = A @ B^T + gate(dy, mask) (GATE above): what tfosr_gemm_bt_acc()
+// leaves in a C that held the gated gradient, bit for bit, on the tile shape
+// it would pick. Only for shapes with tfosr_gemm_bt_gate_eligible().
+void tfosr_gemm_bt_gate(const void* A, const void* B, const void* dy,
+                        const unsigned char* mask, void* C, int M, int N,
+                        int K, hipStream_t s) {
+  if (gemm_route_skinny(N)) {
+    dim3 grid(((M + 255) / 256) * ((N + 63) / 64));
+    hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 4, 1, false, false, true>),
+                       grid, dim3(256), 0, s, (const bf16_t*)A,
+                       (const bf16_t*)B, (bf16_t*)C, M, N, K, nullptr,
+                       (const bf16_t*)dy, mask);
+    return;
+  }
+  dim3 grid(((M + 127) / 128) * ((N + 127) / 128));
+  hipLaunchKernelGGL((gemm_bt_kernel<bf16_t, 2, 2, false, false, true>), grid,
+                     dim3(256), 0, s, (const bf16_t*)A, (const bf16_t*)B,
+                     (bf16_t*)C, M, N, K, nullptr, (const bf16_t*)dy, mask);
 }
 
 void tfosr_mfma_probe(const short* a, const short* b, float* c, hipStream_t s) {

@@ -1953,6 +1953,70 @@ def _bn_epi_route(mode, kind, M, K, cout, ext=None):
     return mode == "force" or _bn_epi_auto(kind, M, K, cout)
 
 
+def _bn_gate_mode():
+    """TFOS_BN_GATE: how the backward of a fused bottleneck without a
+    downsample branch forms dx = gate(dy) + conv1 dgrad. 'off': bn_bwd writes
+    the gated gradient out and gemm_bt_acc accumulates into it; 'force':
+    gemm_bt_gate gates dy by the ReLU bitmask in its own epilogue, wherever
+    _bn_gate_route finds the block eligible, and the gated tensor is never
+    written; 'auto' (default): per join size, _bn_gate_auto. Both routes
+    compute the same bits."""
+    mode = os.environ.get("TFOS_BN_GATE", "auto")
+    if mode not in ("auto", "off", "force"):
+        raise ValueError("TFOS_BN_GATE must be auto, off or force, got "
+                         + repr(mode))
+    return mode
+
+
+# smallest join tensor, in bytes, that TFOS_BN_GATE=auto routes: the smallest
+# tensor the measurement below found ahead (1024 x 2048 x 7 x 7 bf16, 206 MB)
+_BN_GATE_MIN_BYTES = 1024 * 2048 * 7 * 7 * 2
+
+
+def _bn_gate_auto(nbytes):
+    """TFOS_BN_GATE=auto policy for one identity block whose join tensor
+    (dy, t3) has ``nbytes`` bytes.
+
+    Follows the per-pair measurement at the four ResNet-50 batch-1024 join
+    sizes and one size below them (tools/bn_bench.py --gate;
+    docs/performance.md "Gating the residual gradient in the dgrad
+    epilogue"): bn_bwd with the gated-gradient write + gemm_bt_acc against
+    bn_bwd without it + gemm_bt_gate, medians of 9 alternating rounds, a size
+    being ahead when the new chain wins by more than either side's max - min
+    over the rounds.
+
+      1644 MB (256 @56)   2.681 -> 2.439 ms   ahead
+       822 MB (512 @28)   1.394 -> 1.304 ms   ahead
+       411 MB (1024 @14)  0.760 -> 0.738 ms   ahead
+       206 MB (2048 @7)   0.468 -> 0.453 ms   ahead
+        51 MB (32 x 256 @56)  0.088 -> 0.079 ms, less than the old chain's
+                              spread of 0.010 ms: not ahead
+
+    Nothing smaller than the smallest size found ahead is routed."""
+    return nbytes >= _BN_GATE_MIN_BYTES
+
+
+def _bn_gate_route(mode, t3, mask, k_dim, ext=None):
+    """Does an identity block's backward take gemm_bt_gate? Under 'auto' and
+    'force' alike only where the mask is the per-vector byte format (one byte
+    per 8 bf16 elements: what the NHWC fast path of bn_fwd_train and
+    bn_fwd_train_pre writes; the row tier and the generic kernels write no
+    mask and gate from y), C3 % 8 == 0, and the GEMM launcher has a gating
+    epilogue for the shape (``ext.gemm_bt_gate_eligible``). Without ``ext``
+    only the mode, the mask format and the size policy are consulted."""
+    if mode == "off":
+        return False
+    C3 = t3.shape[1]
+    M = t3.numel() // C3
+    if t3.dtype != torch.bfloat16 or C3 % 8 != 0 \
+            or mask.numel() * 8 != t3.numel():
+        return False
+    if mode != "force" and not _bn_gate_auto(t3.numel() * 2):
+        return False    # before any call into ext: a block left alone makes
+                        # exactly the calls it made before
+    return ext is None or bool(ext.gemm_bt_gate_eligible(M, C3, k_dim))
+
+
 class _BottleneckFn(torch.autograd.Function):
     """One autograd node for the whole bottleneck block.
 
@@ -2088,11 +2152,17 @@ class _BottleneckFn(torch.autograd.Function):
 
         # block tail: bn3(+res+relu) backward -> dt3 plus the gated residual
         # gradient dres (doubles as the dx accumulation buffer below)
+        # TFOS_BN_GATE: an identity block whose conv1 dgrad gates dy by the
+        # bn3 mask in its own epilogue never writes dres out
+        gate = not has_down and _bn_gate_route(_bn_gate_mode(), t3, k3, C1,
+                                               ext)
         if dual:
             # both BNs of the join from one read of dy: dres never exists
             td, md, rd = opt
             dt3, dtd, dg3, dgd, db3, dbd = ext.bn_dual_bwd(
                 t3, td, dy, k3, g3, m3, r3, gd, md, rd)
+        elif gate:
+            dt3, dg3, db3 = ext.bn_bwd(t3, dy, y, k3, g3, m3, r3, True, False)
         else:
             dt3, dg3, db3, dres = ext.bn_bwd(t3, dy, y, k3, g3, m3, r3,
                                              True, True)
@@ -2143,9 +2213,14 @@ class _BottleneckFn(torch.autograd.Function):
                 # even-even parity class only; odd pixels' contribution is 0
                 ext.conv_par(dtd, wdbT, dx, [0], [0], 0, True)
         else:
-            # dx = dres + conv1_dgrad — accumulate straight into dres
-            dx = dres
-            ext.gemm_bt_acc(as2d(dt1), w1bT, as2d(dx))
+            if gate:
+                # dx = gate(dy) + conv1_dgrad, gated in the dgrad epilogue
+                dx = as4d(ext.gemm_bt_gate(as2d(dt1), w1bT, as2d(dy), k3),
+                          N, H, W)
+            else:
+                # dx = dres + conv1_dgrad — accumulate straight into dres
+                dx = dres
+                ext.gemm_bt_acc(as2d(dt1), w1bT, as2d(dx))
             dwd = dgd = dbd = None
 
         return (dx, dw1, dg1, db1, None, None, dw2, dg2, db2, None, None,

@@ -34,6 +34,11 @@ on against off (the generic kernels), see ``rows_main``.
 ``--stempool`` is a fourth: the stem's BatchNorm + ReLU + max-pool as three ops
 against the fused kernels of csrc/bn_pool.hip, see ``stempool_main``.
 
+``--gate`` is a fifth: the backward tail of an identity bottleneck, ``bn_bwd``
+writing the gated gradient + ``gemm_bt_acc`` against ``bn_bwd`` without it +
+``gemm_bt_gate``, see ``gate_main``; it is what the ``TFOS_BN_GATE=auto`` rule
+was read off.
+
 The variants timed are the ones the ResNet-50 step runs most: stats; apply
 with ReLU (and with ReLU + residual, ``apply+res``); bwd stats with the mask
 (and writing the gated gradient, ``bwd stats+g``); bwd dx with the mask.
@@ -476,6 +481,90 @@ def stempool_main(args):
             json.dump(records, f, indent=1)
 
 
+# --gate shapes: the join (batch, C3, H=W, C1, identity blocks per step) of
+# the ResNet-50 identity bottlenecks at b1024 and one size below them
+GATE_SHAPES = [(32, 256, 56, 64, 0), (1024, 256, 56, 64, 2),
+               (1024, 512, 28, 128, 3), (1024, 1024, 14, 256, 5),
+               (1024, 2048, 7, 512, 2)]
+
+
+def gate_main(args):
+    """--gate: the tail of an identity bottleneck's backward as two chains on
+    the same tensors, alternating inside every round: ``old`` is bn_bwd
+    writing the gated gradient out (relu, grad_res) + gemm_bt_acc into it,
+    ``new`` is bn_bwd without that write + gemm_bt_gate, which gates dy by
+    the mask in its own epilogue. Columns: medians over the rounds, each
+    side's spread (max - min over the rounds), old - new; a size is ahead
+    when old - new exceeds the larger spread. The ``TFOS_BN_GATE=auto`` rule
+    in ops/modules.py routes from the smallest size that is ahead."""
+    from tensorflowonspark_amd.ops import get_ext
+    ext = get_ext(required=True)
+    dev, bf = "cuda", torch.bfloat16
+    print("identity-block join, bf16: ms per chain, median of {} rounds x {} "
+          "launches".format(args.rounds, args.iters))
+    print("{:>5s} {:>5s} {:>3s} {:>4s} {:>2s} {:>6s} | {:>8s} {:>8s} {:>7s} "
+          "{:>7s} | {:>8s} {}".format("batch", "C3", "H", "C1", "n", "MB",
+                                      "old", "new", "sprd o", "sprd n",
+                                      "old-new", "verdict"))
+    records = []
+    step_old = step_new = 0.0
+    for N, C3, H, C1, count in GATE_SHAPES:
+        shape = (N, C3, H, H)
+
+        def act(s=shape):
+            return torch.randn(s, device=dev).to(bf).contiguous(
+                memory_format=torch.channels_last)
+
+        t3, res, dy = act(), act(), act()
+        dt1 = act((N, C1, H, H)).permute(0, 2, 3, 1).reshape(-1, C1)
+        w1bT = (torch.randn(C3, C1, device=dev) / C1 ** 0.5).to(bf)
+        w, b = torch.rand(C3, device=dev) + 0.5, torch.randn(C3, device=dev)
+        rm, rv = torch.zeros(C3, device=dev), torch.ones(C3, device=dev)
+        # one real forward: y, the mask and the statistics as training has them
+        y, mean, rstd, mask = ext.bn_fwd_train(t3, res, w, b, rm, rv, 0.1,
+                                               1e-5, True)
+        del res
+        dy2d = dy.permute(0, 2, 3, 1).reshape(-1, C3)
+        assert ext.gemm_bt_gate_eligible(dt1.shape[0], C3, C1)
+
+        def old():
+            _, _, _, dres = ext.bn_bwd(t3, dy, y, mask, w, mean, rstd, True,
+                                       True)
+            return ext.gemm_bt_acc(dt1, w1bT,
+                                   dres.permute(0, 2, 3, 1).reshape(-1, C3))
+
+        def new():
+            ext.bn_bwd(t3, dy, y, mask, w, mean, rstd, True, False)
+            return ext.gemm_bt_gate(dt1, w1bT, dy2d, mask)
+
+        assert torch.equal(old(), new()), "the two chains differ"
+        torch.cuda.synchronize()
+        ms = {"old": [], "new": []}
+        for _ in range(args.rounds):
+            for n, fn in (("old", old), ("new", new)):
+                ms[n].append(time_round(fn, args.iters))
+        med = {n: statistics.median(v) for n, v in ms.items()}
+        spr = {n: max(v) - min(v) for n, v in ms.items()}
+        gain = med["old"] - med["new"]
+        ahead = gain > max(spr.values())
+        step_old += count * med["old"]
+        step_new += count * med["new"]
+        records.append({"shape": shape, "C1": C1, "count": count,
+                        "old_ms": ms["old"], "new_ms": ms["new"]})
+        print("{:5d} {:5d} {:3d} {:4d} {:2d} {:6.0f} | {:8.4f} {:8.4f} {:7.4f} "
+              "{:7.4f} | {:8.4f} {}".format(
+                  N, C3, H, C1, count, t3.numel() * 2 / 1e6, med["old"],
+                  med["new"], spr["old"], spr["new"], gain,
+                  "ahead" if ahead else "NOT ahead"), flush=True)
+        del t3, dy, dy2d, y, mask, dt1
+        torch.cuda.empty_cache()
+    print("per step (blocks x medians), ms: old {:.3f}  new {:.3f}".format(
+        step_old, step_new))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(records, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1024)
@@ -492,12 +581,17 @@ def main():
     ap.add_argument("--stempool", action="store_true",
                     help="the stem's BatchNorm + ReLU + max-pool: three ops vs "
                          "the fused entries")
+    ap.add_argument("--gate", action="store_true",
+                    help="identity-block join: bn_bwd + gemm_bt_acc vs the "
+                         "mask-gating dgrad epilogue (gemm_bt_gate)")
     ap.add_argument("--json", metavar="PATH",
-                    help="with --rows or --stempool: also write every round's "
-                         "times here")
+                    help="with --rows, --stempool or --gate: also write every "
+                         "round's times here")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bn_bench needs a GPU")
+    if args.gate:
+        return gate_main(args)
     if args.stempool:
         return stempool_main(args)
     if args.rows:
