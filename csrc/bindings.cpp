@@ -1254,6 +1254,52 @@ void cv_check_device(const char* op, const char* name, const at::Tensor& t,
               ref.device(), ", got ", t.device());
 }
 
+// The streaming ops (depthwise, transposed-conv head and weight gradient,
+// pointwise, bilinear upsampling) take empty tensors and vector-load 16 B.
+// What kind of tensor an activation or gradient of theirs is: 4-D on a GPU,
+// bf16 (or fp32 where fp32_ok). Returns true when it is empty: nothing to
+// launch, and its layout is not looked at.
+bool st_check_kind(const char* op, const char* name, const at::Tensor& t,
+                   bool fp32_ok) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.dim() == 4, op, ": ", name, " must be 4-D (N, C, H, W), got ",
+              t.dim(), "-D");
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 ||
+                  (fp32_ok && t.scalar_type() == at::kFloat),
+              op, ": ", name, fp32_ok ? " must be bf16 or fp32, got "
+                                      : " must be bf16, got ",
+              t.scalar_type());
+  return t.numel() == 0;
+}
+
+// st_check_kind, and a tensor that is not empty is channels_last-contiguous
+// with its base on the 16 B grid. Each op's own limits follow at the caller.
+bool st_check_act(const char* op, const char* name, const at::Tensor& t,
+                  bool fp32_ok) {
+  if (st_check_kind(op, name, t, fp32_ok)) return true;
+  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name,
+              " must be channels_last-contiguous");
+  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
+              " must be 16-byte aligned");
+  return false;
+}
+
+// The module's own parameter of a streaming op: on the activation's device,
+// contiguous 4-D fp32 (or bf16 where bf16_ok) with a k x k filter. ``what``
+// names the shape in the message; the channel relations are the caller's.
+void st_check_weight(const char* op, const at::Tensor& w,
+                     const at::Tensor& act, bool bf16_ok, long k,
+                     const std::string& what) {
+  cv_check_device(op, "weight", w, act);
+  TORCH_CHECK((w.scalar_type() == at::kFloat ||
+               (bf16_ok && w.scalar_type() == at::kBFloat16)) &&
+                  w.dim() == 4 && w.size(2) == k && w.size(3) == k &&
+                  w.is_contiguous(),
+              op, ": weight must be the contiguous ",
+              bf16_ok ? "fp32 or bf16 " : "fp32 ", what, ", got ",
+              w.scalar_type(), " ", w.sizes());
+}
+
 // A weight matrix: 2-D bf16 [rows, cols] on the activation's device (every
 // caller passes it 2-D). It need not be contiguous: the entries launch on
 // w.contiguous().
@@ -1765,20 +1811,10 @@ static int dw_vec(const at::Tensor& t) {
 // tensor is empty (nothing to launch).
 static bool dw_check_act(const char* op, const char* name,
                          const at::Tensor& t) {
-  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
-  TORCH_CHECK(t.dim() == 4, op, ": ", name, " must be 4-D (N, C, H, W), got ",
-              t.dim(), "-D");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16 ||
-                  t.scalar_type() == at::kFloat,
-              op, ": ", name, " must be bf16 or fp32, got ", t.scalar_type());
-  if (t.numel() == 0) return true;
-  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name,
-              " must be channels_last-contiguous");
+  if (st_check_act(op, name, t, true)) return true;
   const int V = dw_vec(t);
   TORCH_CHECK(t.size(1) % V == 0, op, ": C=", t.size(1),
               " must be a multiple of ", V, " for ", t.scalar_type());
-  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
-              " must be 16-byte aligned");
   TORCH_CHECK(t.numel() / V < (1L << 31), op, ": ", name, " has ", t.numel(),
               " elements, more than the kernels index");
   return false;
@@ -1786,14 +1822,12 @@ static bool dw_check_act(const char* op, const char* name,
 
 static void dw_check_weight(const char* op, const at::Tensor& w,
                             const at::Tensor& act) {
-  TORCH_CHECK(w.device() == act.device(), op, ": weight must be on ",
-              act.device(), ", got ", w.device());
-  TORCH_CHECK(w.scalar_type() == at::kFloat && w.dim() == 4 &&
-                  w.size(0) == act.size(1) && w.size(1) == 1 &&
-                  w.size(2) == 3 && w.size(3) == 3 && w.is_contiguous(),
-              op, ": weight must be the contiguous fp32 [C,1,3,3] parameter "
-              "with C=", act.size(1), ", got ", w.scalar_type(), " ",
-              w.sizes());
+  const std::string what =
+      "[C,1,3,3] parameter with C=" + std::to_string(act.size(1));
+  st_check_weight(op, w, act, false, 3, what);
+  TORCH_CHECK(w.size(0) == act.size(1) && w.size(1) == 1, op,
+              ": weight must be the contiguous fp32 ", what, ", got ",
+              w.scalar_type(), " ", w.sizes());
 }
 
 static void dw_check_stride(const char* op, long stride) {
@@ -1885,16 +1919,7 @@ static at::Tensor dwconv3x3_wrw(at::Tensor dy, at::Tensor x, long stride) {
 // tensor is empty (nothing to launch).
 static bool cth_check_act(const char* op, const char* name,
                           const at::Tensor& t) {
-  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
-  TORCH_CHECK(t.dim() == 4, op, ": ", name, " must be 4-D (N, C, H, W), got ",
-              t.dim(), "-D");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16, op, ": ", name,
-              " must be bf16, got ", t.scalar_type());
-  if (t.numel() == 0) return true;
-  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name,
-              " must be channels_last-contiguous");
-  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
-              " must be 16-byte aligned");
+  if (st_check_act(op, name, t, false)) return true;
   TORCH_CHECK(t.numel() < (1L << 31), op, ": ", name, " has ", t.numel(),
               " elements, more than the kernels index");
   return false;
@@ -1909,12 +1934,7 @@ static void cth_check_channels(const char* op, long Cin, long Cout) {
 
 static void cth_check_weight(const char* op, const at::Tensor& w,
                              const at::Tensor& act) {
-  TORCH_CHECK(w.device() == act.device(), op, ": weight must be on ",
-              act.device(), ", got ", w.device());
-  TORCH_CHECK(w.scalar_type() == at::kFloat && w.dim() == 4 &&
-                  w.size(2) == 4 && w.size(3) == 4 && w.is_contiguous(),
-              op, ": weight must be the contiguous fp32 [Cin,Cout,4,4] "
-              "parameter, got ", w.scalar_type(), " ", w.sizes());
+  st_check_weight(op, w, act, false, 4, "[Cin,Cout,4,4] parameter");
 }
 
 static at::Tensor convt_head_fwd(at::Tensor x, at::Tensor w,
@@ -2059,16 +2079,9 @@ static py::dict convt_wrw_plan(long N, long H, long W, long Cin, long Cout) {
 
 static at::Tensor convt_wrw(at::Tensor dy, at::Tensor x) {
   const char* op = "convt_wrw";
-  const at::Tensor* ts[2] = {&dy, &x};
-  const char* names[2] = {"dy", "x"};
-  for (int i = 0; i < 2; ++i) {
-    TORCH_CHECK(ts[i]->is_cuda(), op, ": ", names[i],
-                " must be a GPU tensor");
-    TORCH_CHECK(ts[i]->dim() == 4, op, ": ", names[i],
-                " must be 4-D (N, C, H, W), got ", ts[i]->dim(), "-D");
-    TORCH_CHECK(ts[i]->scalar_type() == at::kBFloat16, op, ": ", names[i],
-                " must be bf16, got ", ts[i]->scalar_type());
-  }
+  // the layout is ctw_check_act's: a channel slice passes here
+  const bool dy_empty = st_check_kind(op, "dy", dy, false);
+  const bool x_empty = st_check_kind(op, "x", x, false);
   cv_check_device(op, "x", x, dy);
   const long N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
   const long Cout = dy.size(1);
@@ -2076,8 +2089,7 @@ static at::Tensor convt_wrw(at::Tensor dy, at::Tensor x) {
               op, ": x ", x.sizes(), " gives a gradient of [", N, ", Cout, ",
               2 * H, ", ", 2 * W, "], got ", dy.sizes());
   auto opts = x.options().dtype(at::kFloat);
-  if (x.numel() == 0 || dy.numel() == 0)
-    return at::zeros({Cin, Cout, 4, 4}, opts);
+  if (dy_empty || x_empty) return at::zeros({Cin, Cout, 4, 4}, opts);
   const long dps = ctw_check_act(op, "dy", dy);
   const long xps = ctw_check_act(op, "x", x);
   const py::dict plan = convt_wrw_plan(N, H, W, Cin, Cout);
@@ -2121,19 +2133,14 @@ static void pw_check_channels(const char* op, const char* name, long C) {
               " must be a multiple of 8 in [8, ", max_c, "]");
 }
 
-// An activation or gradient as the kernels take it: cv_check_act, but an
-// empty tensor passes (returns true: nothing to launch), the base must sit
-// on the 16 B grid of the vector accesses, and N*H*W must fit the kernels'
-// 32-bit pixel index.
+// An activation or gradient as the kernels take it. Returns true when the
+// tensor is empty (nothing to launch); one that is not also meets
+// cv_check_act's size limits, and N*H*W fits the kernels' 32-bit pixel index.
 static bool pw_check_act(const char* op, const char* name,
                          const at::Tensor& t) {
-  if (t.is_cuda() && t.dim() == 4 && t.scalar_type() == at::kBFloat16 &&
-      t.numel() == 0)
-    return true;
+  if (st_check_act(op, name, t, false)) return true;
   cv_check_act(op, name, t, 8);
   pw_check_channels(op, name, t.size(1));
-  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
-              " must be 16-byte aligned");
   TORCH_CHECK(t.numel() / t.size(1) <= INT_MAX, op, ": ", name, " has ",
               t.numel() / t.size(1), " pixels, more than the 32-bit pixel "
               "index holds");
@@ -2142,14 +2149,7 @@ static bool pw_check_act(const char* op, const char* name,
 
 static void pw_check_weight(const char* op, const at::Tensor& w,
                             const at::Tensor& act) {
-  cv_check_device(op, "weight", w, act);
-  TORCH_CHECK((w.scalar_type() == at::kFloat ||
-               w.scalar_type() == at::kBFloat16) &&
-                  w.dim() == 4 && w.size(2) == 1 && w.size(3) == 1 &&
-                  w.is_contiguous(),
-              op, ": weight must be the contiguous fp32 or bf16 "
-              "[Cout,Cin,1,1] parameter, got ", w.scalar_type(), " ",
-              w.sizes());
+  st_check_weight(op, w, act, true, 1, "[Cout,Cin,1,1] parameter");
   pw_check_channels(op, "Cout", w.size(0));
   pw_check_channels(op, "Cin", w.size(1));
 }
@@ -2200,22 +2200,14 @@ static int ub_max_c() {
   return v[8];
 }
 
-// The tensor as the kernels take it. Returns true when it is empty.
+// The tensor as the kernels take it. Returns true when it is empty, which an
+// image without rows or columns is not allowed to be.
 static bool ub_check_act(const char* op, const char* name,
                          const at::Tensor& t) {
-  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
-  TORCH_CHECK(t.dim() == 4, op, ": ", name, " must be 4-D (N, C, H, W), got ",
-              t.dim(), "-D");
-  TORCH_CHECK(t.scalar_type() == at::kBFloat16 ||
-                  t.scalar_type() == at::kFloat,
-              op, ": ", name, " must be bf16 or fp32, got ", t.scalar_type());
+  const bool empty = st_check_act(op, name, t, true);
   TORCH_CHECK(t.size(2) >= 1 && t.size(3) >= 1, op, ": ", name,
               " must have at least one row and column, got ", t.sizes());
-  if (t.numel() == 0) return true;
-  TORCH_CHECK(t.is_contiguous(at::MemoryFormat::ChannelsLast), op, ": ", name,
-              " must be channels_last-contiguous");
-  TORCH_CHECK((uintptr_t)t.data_ptr() % 16 == 0, op, ": ", name,
-              " must be 16-byte aligned");
+  if (empty) return true;
   TORCH_CHECK(t.size(1) <= ub_max_c(), op, ": C=", t.size(1),
               " must be at most ", ub_max_c());
   return false;

@@ -23,6 +23,53 @@ def _cl_bf16(t):
     return t.contiguous(memory_format=torch.channels_last).to(torch.bfloat16)
 
 
+def _cl_grad(dy, dtype):
+    """An upstream gradient as a real channels_last tensor of ``dtype``: an
+    expanded (stride-0) one, as from y.sum().backward(), becomes real here."""
+    return dy.to(dtype).contiguous(memory_format=torch.channels_last)
+
+
+def _autocast_dtype(x):
+    """The dtype a routed module computes in: under autocast the library
+    would run in the autocast dtype whatever x is, and so do the kernels."""
+    return torch.get_autocast_dtype("cuda") \
+        if torch.is_autocast_enabled("cuda") else x.dtype
+
+
+def _apply_routed(fn, route, x, dt, *args):
+    """``fn.apply(x, *args, *route)`` on x made channels_last in ``dt``, or
+    None where ``route`` is None: the caller's library path."""
+    if route is None or get_ext(required=True) is None:
+        return None
+    x = x.to(dt).contiguous(memory_format=torch.channels_last)
+    return fn.apply(x, *args, *route)
+
+
+def _env_mode(var, allowed, default="auto"):
+    """A routing switch, read from the environment at call time: one of
+    ``allowed``, ``default`` when unset."""
+    mode = os.environ.get(var, default)
+    if mode not in allowed:
+        raise ValueError("{} must be {} or {}, got {!r}".format(
+            var, ", ".join(allowed[:-1]), allowed[-1], mode))
+    return mode
+
+
+def _nearest_row(rows, key, want, size):
+    """The row of a measured table that decides for a shape: the first whose
+    leading columns equal ``key``; else the one whose ``size(row)`` is nearest
+    to ``want`` (floored at 1) in ratio, the first of those that tie."""
+    want = float(max(1, want))
+
+    def dist(r):
+        have = float(size(r))
+        return max(have / want, want / have)
+
+    n = len(key)
+    exact = [r for r in rows if r[:n] == key]
+    return exact[0] if exact else min(rows, key=dist)
+
+
 def _cl_alloc(shape, device, dtype=torch.bfloat16, zero=False):
     """A fresh tensor of ``shape`` that is channels_last from birth.
 
@@ -89,6 +136,24 @@ def _lib_conv_backward(dy, x, weight, stride, pad, fd, transposed, mask):
     return gx, gw
 
 
+def _lib_conv_rest(dy, x, weight, grads, need, stride, pad, groups=1,
+                   transposed=False, bias_sizes=None):
+    """(dx, dw, db) of a routed conv, completed by the library: whatever
+    ``need`` asks for and ``grads`` still holds as None comes from one
+    aten.convolution_backward call on the weight cast to x's dtype, dw and db
+    in the weight's own dtype."""
+    mask = [n and g is None for n, g in zip(need, grads)]
+    if not any(mask):
+        return grads
+    lib = torch.ops.aten.convolution_backward(
+        dy, x, weight.to(x.dtype), bias_sizes, [stride, stride], [pad, pad],
+        [1, 1], transposed, [0, 0], groups, mask)
+    dx, dw, db = grads
+    return (lib[0] if mask[0] else dx,
+            lib[1].to(weight.dtype) if mask[1] else dw,
+            lib[2].to(weight.dtype) if mask[2] else db)
+
+
 def _ctw_table():
     """(Cin, Cout, H, W, smallest N) per U-Net up-stack class where
     tools/convt_wrw_bench.py measured csrc/convt_wrw.hip no slower than the
@@ -115,12 +180,9 @@ def _ctw_route(x, dy_hw, cin, cout, k, stride, pad):
     of this ConvTranspose2d to convt_wrw? x: the layer's input; dy_hw: the
     output's (H, W), which is (2H, 2W) exactly when output_padding is 0.
     TFOS_WRW has no say in it."""
-    mode = os.environ.get("TFOS_CONVT_WRW", "auto")
+    mode = _env_mode("TFOS_CONVT_WRW", ("auto", "hip", "miopen"))
     if mode == "miopen":
         return False
-    if mode not in ("hip", "auto"):
-        raise ValueError("TFOS_CONVT_WRW must be auto, hip or miopen, got "
-                         + repr(mode))
     N, _, H, W = x.shape
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.numel() > 0
             and (k, stride, pad) == (4, 2, 1)
@@ -795,12 +857,9 @@ def _atrous_auto(path, M, cin, cout):
 def _atrous_route(N, H, W, cin, cout, fd):
     """(collapse, fwd_in_tree, dgrad_in_tree) for TFOS_ATROUS, or None for
     the plain library conv."""
-    mode = os.environ.get("TFOS_ATROUS", "auto")
+    mode = _env_mode("TFOS_ATROUS", ("auto", "mfma", "miopen"))
     if mode == "miopen":
         return None
-    if mode not in ("auto", "mfma"):
-        raise ValueError("TFOS_ATROUS must be auto, mfma or miopen, got "
-                         + repr(mode))
     centre_only = live_taps(H, W, 3, 1, fd, fd) == ((1,), (1,))
     if mode == "mfma":
         return centre_only, True, True
@@ -916,15 +975,9 @@ class DilatedConv3x3(nn.Conv2d):
         return super().forward(x)
 
     def __prepare_scriptable__(self):
-        # the scripter must not compile the routed forward: hand it a plain
-        # conv that shares the weight and carries dilation and padding
-        _SCRIPT_CLONE_KEEPALIVE.append(self)
-        new = nn.Conv2d(self.in_channels, self.out_channels, 3, stride=1,
-                        padding=self.padding, dilation=self.dilation,
-                        bias=False)
-        new.weight = self.weight
-        new.train(self.training)
-        return new
+        return _plain_clone(self, nn.Conv2d(
+            self.in_channels, self.out_channels, 3, stride=1,
+            padding=self.padding, dilation=self.dilation, bias=False))
 
 
 # ---------------------------------------------------------------------------
@@ -951,17 +1004,10 @@ def _dw_auto(direction, N, C, H, W, stride):
     stand against the library follows the tensor size. A stride that was
     never measured (there is none among {1, 2}) stays on the library."""
     rows = [r for r in _dw_table() if r[4] == stride]
-    if not rows:
-        return False
-    want = float(max(1, N * C * H * W))
-
-    def dist(r):
-        have = float(r[0] * r[1] * r[2] * r[3])
-        return max(have / want, want / have)
-
-    exact = [r for r in rows if r[:4] == (N, C, H, W)]
-    row = exact[0] if exact else min(rows, key=dist)
-    return row[5 + _DW_DIRECTIONS.index(direction)]
+    return bool(rows) and _nearest_row(
+        rows, (N, C, H, W), N * C * H * W,
+        lambda r: r[0] * r[1] * r[2] * r[3])[
+            5 + _DW_DIRECTIONS.index(direction)]
 
 
 def _dw_table():
@@ -997,14 +1043,11 @@ def _dw_table():
 def _dw_route(N, C, H, W, stride):
     """(fwd_in_tree, dgrad_in_tree, wrw_in_tree) for TFOS_DW, or None for
     the plain library conv."""
-    mode = os.environ.get("TFOS_DW", "auto")
+    mode = _env_mode("TFOS_DW", ("auto", "hip", "miopen"))
     if mode == "miopen":
         return None
     if mode == "hip":
         return True, True, True
-    if mode != "auto":
-        raise ValueError("TFOS_DW must be auto, hip or miopen, got "
-                         + repr(mode))
     route = tuple(_dw_auto(d, N, C, H, W, stride) for d in _DW_DIRECTIONS)
     return route if any(route) else None
 
@@ -1035,25 +1078,16 @@ class _DepthwiseFn(torch.autograd.Function):
         stride = ctx.stride
         dgrad_in_tree, wrw_in_tree = ctx.in_tree
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        # an expanded (stride-0) gradient, as from y.sum().backward(),
-        # becomes a real channels_last tensor here
-        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        dy = _cl_grad(dy, x.dtype)
         dx = dw = None
         if need_dx and dgrad_in_tree:
             dx = get_ext(required=True).dwconv3x3_dgrad(
                 dy, weight, stride, x.shape[2], x.shape[3])
         if need_dw and wrw_in_tree:
             dw = get_ext(required=True).dwconv3x3_wrw(dy, x, stride)
-        lib_dx = need_dx and dx is None
-        lib_dw = need_dw and dw is None
-        if lib_dx or lib_dw:
-            gx, gw, _ = torch.ops.aten.convolution_backward(
-                dy, x, weight.to(x.dtype), None, [stride, stride], [1, 1],
-                [1, 1], False, [0, 0], x.shape[1], [lib_dx, lib_dw, False])
-            if lib_dx:
-                dx = gx
-            if lib_dw:
-                dw = gw.to(weight.dtype)
+        dx, dw, _ = _lib_conv_rest(dy, x, weight, (dx, dw, None),
+                                   (need_dx, need_dw, False), stride, 1,
+                                   groups=x.shape[1])
         return dx, dw, None, None, None, None
 
 
@@ -1082,31 +1116,22 @@ class DepthwiseConv3x3(nn.Conv2d):
 
     def forward(self, x):
         if x.is_cuda and x.dim() == 4 and self.weight.dtype == torch.float32:
-            # under autocast the library conv would run in the autocast
-            # dtype whatever x is; so does this path
-            dt = torch.get_autocast_dtype("cuda") \
-                if torch.is_autocast_enabled("cuda") else x.dtype
+            dt = _autocast_dtype(x)
             C = self.in_channels
             vec = {torch.bfloat16: 8, torch.float32: 4}.get(dt)
             if vec is not None and C % vec == 0 and x.numel() > 0:
                 route = _dw_route(x.shape[0], C, x.shape[2], x.shape[3],
                                   self.stride[0])
-                if route is not None and get_ext(required=True) is not None:
-                    x = x.to(dt).contiguous(memory_format=torch.channels_last)
-                    return _DepthwiseFn.apply(x, self.weight, self.stride[0],
-                                              *route)
+                y = _apply_routed(_DepthwiseFn, route, x, dt, self.weight,
+                                  self.stride[0])
+                if y is not None:
+                    return y
         return super().forward(x)
 
     def __prepare_scriptable__(self):
-        # the scripter must not compile the routed forward: hand it a plain
-        # grouped conv that shares the weight
-        _SCRIPT_CLONE_KEEPALIVE.append(self)
-        new = nn.Conv2d(self.in_channels, self.out_channels, 3,
-                        stride=self.stride, padding=1, groups=self.groups,
-                        bias=False)
-        new.weight = self.weight
-        new.train(self.training)
-        return new
+        return _plain_clone(self, nn.Conv2d(
+            self.in_channels, self.out_channels, 3, stride=self.stride,
+            padding=1, groups=self.groups, bias=False))
 
 
 # ---------------------------------------------------------------------------
@@ -1169,28 +1194,19 @@ def _pw_auto(N, cin, cout, H, W):
     measured takes the row whose M * (cin + cout), the bytes forward and
     dgrad move, is nearest in ratio (these are streaming kernels, as in
     _dw_auto)."""
-    rows = _pw_table()
-    want = float(max(1, N * H * W * (cin + cout)))
-
-    def dist(r):
-        have = float(r[0] * r[3] * r[4] * (r[1] + r[2]))
-        return max(have / want, want / have)
-
-    exact = [r for r in rows if r[:5] == (N, cin, cout, H, W)]
-    return (exact[0] if exact else min(rows, key=dist))[5:]
+    return _nearest_row(
+        _pw_table(), (N, cin, cout, H, W), N * H * W * (cin + cout),
+        lambda r: r[0] * r[3] * r[4] * (r[1] + r[2]))[5:]
 
 
 def _pw_route(N, cin, cout, H, W):
     """(fwd_in_tree, dgrad_in_tree, wrw) for TFOS_PW, wrw one of 'wrw2' and
     'lib'; None for the plain library conv."""
-    mode = os.environ.get("TFOS_PW", "auto")
+    mode = _env_mode("TFOS_PW", ("auto", "hip", "miopen"))
     if mode == "miopen":
         return None
     if mode == "hip":
         return True, True, "wrw2"
-    if mode != "auto":
-        raise ValueError("TFOS_PW must be auto, hip or miopen, got "
-                         + repr(mode))
     route = _pw_auto(N, cin, cout, H, W)
     return None if route == (False, False, "lib") else route
 
@@ -1216,25 +1232,15 @@ class _PointwiseFn(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         dgrad_in_tree, wrw = ctx.route
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        # an expanded (stride-0) gradient, as from y.sum().backward(),
-        # becomes a real channels_last tensor here
-        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        dy = _cl_grad(dy, x.dtype)
         dx = dw = None
         if need_dx and dgrad_in_tree:
             dx = get_ext(required=True).pwconv_dgrad(dy, weight)
         if need_dw and wrw == "wrw2":
             dw = get_ext(required=True).conv_wrw2(dy, x, 1, 1, 1, 0)
             dw = dw.view_as(weight).to(weight.dtype)
-        lib_dx = need_dx and dx is None
-        lib_dw = need_dw and dw is None
-        if lib_dx or lib_dw:
-            gx, gw, _ = torch.ops.aten.convolution_backward(
-                dy, x, weight.to(x.dtype), None, [1, 1], [0, 0], [1, 1],
-                False, [0, 0], 1, [lib_dx, lib_dw, False])
-            if lib_dx:
-                dx = gx
-            if lib_dw:
-                dw = gw.to(weight.dtype)
+        dx, dw, _ = _lib_conv_rest(dy, x, weight, (dx, dw, None),
+                                   (need_dx, need_dw, False), 1, 0)
         return dx, dw, None, None, None
 
 
@@ -1257,29 +1263,21 @@ class PointwiseConv(nn.Conv2d):
 
     def forward(self, x):
         if x.is_cuda and x.dim() == 4 and self.weight.dtype == torch.float32:
-            # under autocast the library conv would run in the autocast
-            # dtype whatever x is; so does this path
-            dt = torch.get_autocast_dtype("cuda") \
-                if torch.is_autocast_enabled("cuda") else x.dtype
+            dt = _autocast_dtype(x)
             cin, cout = self.in_channels, self.out_channels
             N, _, H, W = x.shape
             if (dt == torch.bfloat16 and cin % 8 == 0 and cout % 8 == 0
                     and max(cin, cout) <= _PW_MAX_C
                     and 0 < N * H * W < 2 ** 31):
-                route = _pw_route(N, cin, cout, H, W)
-                if route is not None and get_ext(required=True) is not None:
-                    x = x.to(dt).contiguous(memory_format=torch.channels_last)
-                    return _PointwiseFn.apply(x, self.weight, *route)
+                y = _apply_routed(_PointwiseFn, _pw_route(N, cin, cout, H, W),
+                                  x, dt, self.weight)
+                if y is not None:
+                    return y
         return super().forward(x)
 
     def __prepare_scriptable__(self):
-        # the scripter must not compile the routed forward: hand it a plain
-        # conv that shares the weight
-        _SCRIPT_CLONE_KEEPALIVE.append(self)
-        new = nn.Conv2d(self.in_channels, self.out_channels, 1, bias=False)
-        new.weight = self.weight
-        new.train(self.training)
-        return new
+        return _plain_clone(self, nn.Conv2d(
+            self.in_channels, self.out_channels, 1, bias=False))
 
 
 def _parity_launch(x, class_weight, out, k, pp, accum):
@@ -1457,29 +1455,20 @@ def _cth_auto(direction, N, cin, cout, H, W):
     of the measured one whose input element count is nearest in ratio:
     these are streaming kernels, and how they stand against the library
     follows the tensor size."""
-    rows = _cth_table()
-    want = float(max(1, N * cin * H * W))
-
-    def dist(r):
-        have = float(r[0] * r[1] * r[3] * r[4])
-        return max(have / want, want / have)
-
-    exact = [r for r in rows if r[:5] == (N, cin, cout, H, W)]
-    row = exact[0] if exact else min(rows, key=dist)
-    return row[5 + _CTH_DIRECTIONS.index(direction)]
+    return _nearest_row(
+        _cth_table(), (N, cin, cout, H, W), N * cin * H * W,
+        lambda r: r[0] * r[1] * r[3] * r[4])[
+            5 + _CTH_DIRECTIONS.index(direction)]
 
 
 def _cth_route(N, cin, cout, H, W):
     """(fwd_in_tree, dgrad_in_tree, wrw_in_tree) for TFOS_CONVT_HEAD, or None
     for the plain library call."""
-    mode = os.environ.get("TFOS_CONVT_HEAD", "auto")
+    mode = _env_mode("TFOS_CONVT_HEAD", ("auto", "hip", "miopen"))
     if mode == "miopen":
         return None
     if mode == "hip":
         return True, True, True
-    if mode != "auto":
-        raise ValueError("TFOS_CONVT_HEAD must be auto, hip or miopen, got "
-                         + repr(mode))
     route = tuple(_cth_auto(d, N, cin, cout, H, W) for d in _CTH_DIRECTIONS)
     return route if any(route) else None
 
@@ -1511,27 +1500,16 @@ class _ConvTHeadFn(torch.autograd.Function):
         dgrad_in_tree, wrw_in_tree = ctx.in_tree
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_db = ctx.has_bias and ctx.needs_input_grad[2]
-        # an expanded (stride-0) gradient, as from y.sum().backward(),
-        # becomes a real channels_last tensor here
-        dy = dy.to(x.dtype).contiguous(memory_format=torch.channels_last)
+        dy = _cl_grad(dy, x.dtype)
         dx = dw = db = None
         if need_dx and dgrad_in_tree:
             dx = get_ext(required=True).convt_head_dgrad(
                 dy, weight, x.shape[2], x.shape[3])
         if (need_dw or need_db) and wrw_in_tree:
             dw, db = get_ext(required=True).convt_head_wrw(dy, x)
-        lib_dx = need_dx and dx is None
-        lib_dw = (need_dw or need_db) and dw is None
-        if lib_dx or lib_dw:
-            gx, gw, gb = torch.ops.aten.convolution_backward(
-                dy, x, weight.to(x.dtype), [weight.shape[1]], [2, 2], [1, 1],
-                [1, 1], True, [0, 0], 1, [lib_dx, lib_dw and need_dw,
-                                          lib_dw and need_db])
-            if lib_dx:
-                dx = gx
-            if lib_dw:
-                dw = gw.to(weight.dtype) if need_dw else None
-                db = gb.to(weight.dtype) if need_db else None
+        dx, dw, db = _lib_conv_rest(
+            dy, x, weight, (dx, dw, db), (need_dx, need_dw, need_db), 2, 1,
+            transposed=True, bias_sizes=[weight.shape[1]])
         return (dx, dw if need_dw else None, db if need_db else None,
                 None, None, None)
 
@@ -1558,32 +1536,21 @@ class ConvTranspose2dHead(nn.ConvTranspose2d):
         cin, cout = self.in_channels, self.out_channels
         if x.is_cuda and x.dim() == 4 and output_size is None \
                 and self.weight.dtype == torch.float32:
-            # under autocast the library runs in the autocast dtype whatever
-            # x is; so does this path
-            dt = torch.get_autocast_dtype("cuda") \
-                if torch.is_autocast_enabled("cuda") else x.dtype
+            dt = _autocast_dtype(x)
             if dt == torch.bfloat16 and cin % 8 == 0 and 8 <= cin <= 256 \
                     and 1 <= cout <= 8 and x.numel() > 0:
                 route = _cth_route(x.shape[0], cin, cout, x.shape[2],
                                    x.shape[3])
-                if route is not None and get_ext(required=True) is not None:
-                    x = x.to(dt).contiguous(memory_format=torch.channels_last)
-                    return _ConvTHeadFn.apply(x, self.weight, self.bias,
-                                              *route)
+                y = _apply_routed(_ConvTHeadFn, route, x, dt, self.weight,
+                                  self.bias)
+                if y is not None:
+                    return y
         return super().forward(x, output_size)
 
     def __prepare_scriptable__(self):
-        # the scripter must not compile the routed forward: hand it a plain
-        # transposed conv that shares weight and bias
-        _SCRIPT_CLONE_KEEPALIVE.append(self)
-        new = nn.ConvTranspose2d(self.in_channels, self.out_channels, 4,
-                                 stride=2, padding=1,
-                                 bias=self.bias is not None)
-        new.weight = self.weight
-        if self.bias is not None:
-            new.bias = self.bias
-        new.train(self.training)
-        return new
+        return _plain_clone(self, nn.ConvTranspose2d(
+            self.in_channels, self.out_channels, 4, stride=2, padding=1,
+            bias=self.bias is not None))
 
 
 # ---------------------------------------------------------------------------
@@ -1611,29 +1578,20 @@ def _ub_auto(direction, N, C, Hin, Win, Hout, Wout):
     in-tree? A shape that was not measured takes the decision of the measured
     one whose output element count is nearest in ratio: both directions
     stream the large tensor."""
-    rows = _ub_table()
-    want = float(max(1, N * C * Hout * Wout))
-
-    def dist(r):
-        have = float(r[0] * r[1] * r[4] * r[5])
-        return max(have / want, want / have)
-
-    exact = [r for r in rows if r[:6] == (N, C, Hin, Win, Hout, Wout)]
-    row = exact[0] if exact else min(rows, key=dist)
-    return row[6 + ("fwd", "bwd").index(direction)]
+    return _nearest_row(
+        _ub_table(), (N, C, Hin, Win, Hout, Wout), N * C * Hout * Wout,
+        lambda r: r[0] * r[1] * r[4] * r[5])[
+            6 + ("fwd", "bwd").index(direction)]
 
 
 def _ub_route(N, C, Hin, Win, Hout, Wout):
     """(fwd_in_tree, bwd_in_tree) for TFOS_UPSAMPLE, or None for the plain
     library call."""
-    mode = os.environ.get("TFOS_UPSAMPLE", "auto")
+    mode = _env_mode("TFOS_UPSAMPLE", ("auto", "hip", "aten"))
     if mode == "aten":
         return None
     if mode == "hip":
         return True, True
-    if mode != "auto":
-        raise ValueError("TFOS_UPSAMPLE must be auto, hip or aten, got "
-                         + repr(mode))
     route = tuple(_ub_auto(d, N, C, Hin, Win, Hout, Wout)
                   for d in ("fwd", "bwd"))
     return route if any(route) else None
@@ -1657,9 +1615,7 @@ class _BilinearUpsampleFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         shape, dtype, align_corners, bwd_in_tree = ctx.geom
-        # an expanded (stride-0) gradient, as from y.sum().backward(),
-        # becomes a real channels_last tensor here
-        dy = dy.to(dtype).contiguous(memory_format=torch.channels_last)
+        dy = _cl_grad(dy, dtype)
         if bwd_in_tree:
             dx = get_ext(required=True).upsample_bilinear_bwd(
                 dy, shape[2], shape[3], align_corners)
@@ -1721,10 +1677,7 @@ class BilinearUpsample(nn.Module):
         return bilinear_upsample(x, size, self.align_corners)
 
     def __prepare_scriptable__(self):
-        _SCRIPT_CLONE_KEEPALIVE.append(self)
-        new = _PlainBilinearUpsample(self.align_corners)
-        new.train(self.training)
-        return new
+        return _plain_clone(self, _PlainBilinearUpsample(self.align_corners))
 
 
 # ---------------------------------------------------------------------------
@@ -1900,11 +1853,7 @@ def _bn_epi_mode():
     (stats_nhwc_fast); 'force': the conv kernel's statistics epilogue wherever
     the dispatched kernel has one; 'auto' (default): per shape, _bn_epi_auto.
     """
-    mode = os.environ.get("TFOS_BN_EPI", "auto")
-    if mode not in ("auto", "off", "force"):
-        raise ValueError("TFOS_BN_EPI must be auto, off or force, got "
-                         + repr(mode))
-    return mode
+    return _env_mode("TFOS_BN_EPI", ("auto", "off", "force"))
 
 
 # smallest conv output, in bytes, that TFOS_BN_EPI=auto routes: the smallest
@@ -1961,11 +1910,7 @@ def _bn_gate_mode():
     _bn_gate_route finds the block eligible, and the gated tensor is never
     written; 'auto' (default): per join size, _bn_gate_auto. Both routes
     compute the same bits."""
-    mode = os.environ.get("TFOS_BN_GATE", "auto")
-    if mode not in ("auto", "off", "force"):
-        raise ValueError("TFOS_BN_GATE must be auto, off or force, got "
-                         + repr(mode))
-    return mode
+    return _env_mode("TFOS_BN_GATE", ("auto", "off", "force"))
 
 
 # smallest join tensor, in bytes, that TFOS_BN_GATE=auto routes: the smallest
@@ -2326,11 +2271,7 @@ def _stem_pool_mode():
     """TFOS_STEM_POOL, read at call time: 'on' (default) fuses the stem's
     BatchNorm + ReLU + max-pool where the shape is eligible, 'off' runs the
     three modules one after the other."""
-    mode = os.environ.get("TFOS_STEM_POOL", "on")
-    if mode not in ("on", "off"):
-        raise ValueError("TFOS_STEM_POOL must be on or off, got "
-                         "{!r}".format(mode))
-    return mode
+    return _env_mode("TFOS_STEM_POOL", ("on", "off"), "on")
 
 
 def stem_forward(stem, x):
@@ -2389,36 +2330,40 @@ def _bn_clone(src):
     return bn
 
 
+def _plain_clone(src, new):
+    """``new``, a plain-op twin of the routed module ``src``, made ready to
+    stand in for it: the scripter must not compile a routed forward. It
+    shares src's weight and bias, where src has them, and its mode."""
+    _SCRIPT_CLONE_KEEPALIVE.append(src)
+    for name in ("weight", "bias"):
+        if getattr(src, name, None) is not None:
+            setattr(new, name, getattr(src, name))
+    new.train(src.training)
+    return new
+
+
 def _conv_clone(m):
     """nn.Conv2d equivalent of Conv1x1 / Conv3x3 / StemConv7x7 (or passthrough
     for an already-plain conv)."""
     if isinstance(m, nn.Conv2d):
         return m
-    _SCRIPT_CLONE_KEEPALIVE.append(m)
     k = m.weight.shape[2]
     stride = getattr(m, "stride", 1)
     if isinstance(m, StemConv7x7):
         stride, pad = 2, 3
     else:
         pad = 1 if k == 3 else 0
-    new = nn.Conv2d(m.weight.shape[1], m.weight.shape[0], k, stride=stride,
-                    padding=pad, bias=False)
-    new.weight = m.weight
-    new.train(m.training)
-    return new
+    return _plain_clone(m, nn.Conv2d(m.weight.shape[1], m.weight.shape[0], k,
+                                     stride=stride, padding=pad, bias=False))
 
 
 def _convT_clone(m):
     if isinstance(m, nn.ConvTranspose2d):
         return m
-    _SCRIPT_CLONE_KEEPALIVE.append(m)
-    new = nn.ConvTranspose2d(m.weight.shape[0], m.weight.shape[1],
-                             m.weight.shape[2], stride=m.stride,
-                             padding=m.padding,
-                             output_padding=m.output_padding, bias=False)
-    new.weight = m.weight
-    new.train(m.training)
-    return new
+    return _plain_clone(m, nn.ConvTranspose2d(
+        m.weight.shape[0], m.weight.shape[1], m.weight.shape[2],
+        stride=m.stride, padding=m.padding, output_padding=m.output_padding,
+        bias=False))
 
 
 def _fusedbn_prepare(self):

@@ -207,6 +207,18 @@ def _check(what, got, ref64, ref32, out_dtype, keep=None):
             ref_err))
 
 
+def _off_grid(t):
+    """A copy of channels_last-contiguous ``t`` that starts one element into
+    its buffer: still channels_last-contiguous, its base off the 16 B grid."""
+    assert t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
+    buf = torch.zeros(t.numel() + 8, device=t.device, dtype=t.dtype)
+    view = buf.as_strided(t.shape, t.stride(), 1)
+    view.copy_(t)
+    assert view.is_contiguous(memory_format=torch.channels_last)
+    assert view.data_ptr() % 16 != 0
+    return view
+
+
 def _bits_equal(a, b):
     assert a.dtype == b.dtype and a.shape == b.shape
     view = torch.int16 if a.dtype == BF16 else torch.int32

@@ -17,7 +17,8 @@ import torch
 
 from convt_head_cases import (BF16, CL, FP32, ct_ref, exact_inputs,
                               exact_premise, real_inputs)
-from test_gpu_bn import _DEV, _bits_equal, _ext, _half_ulp, gpu, requires_gpu
+from test_gpu_bn import (_DEV, _bits_equal, _ext, _half_ulp, _off_grid, gpu,
+                         requires_gpu)
 
 # (N, Cin, Cout, H, W); "T" is the forward tile's interior side (14).
 #   1x1            a 2x2 output, only the centre four taps live
@@ -206,6 +207,7 @@ def test_bindings_reject_bad_arguments():
         ("channels_last", lambda: fwd(x.contiguous(), w, b)),
         ("channels_last", lambda: wrw(dy.contiguous(), x)),
         ("channels_last", lambda: dgrad(dy[:1, :1, :1, :1].expand_as(dy), w, 5, 6)),
+        ("16-byte aligned", lambda: fwd(_off_grid(x), w, b)),
         ("4-D", lambda: fwd(x[0], w, b)),
         (r"\[Cin,Cout,4,4\]", lambda: fwd(x, w.to(BF16), b)),
         (r"\[Cin,Cout,4,4\]", lambda: fwd(x, w[:8].contiguous(), b)),

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from convt_wrw_cases import BF16, CASES, CL, case, exact_premise, inputs, wrw_ref
-from test_gpu_bn import _DEV, _bits_equal, _ext, gpu, requires_gpu
+from test_gpu_bn import _DEV, _bits_equal, _ext, _off_grid, gpu, requires_gpu
 
 
 def _canon(t):
@@ -101,6 +101,7 @@ def test_bindings_reject_bad_arguments():
         ("channels_last", lambda: wrw(dy, x[:1, :1, :1, :1].expand_as(x))),
         ("channels_last", lambda: wrw(dy, act(2, 16, 6, 5).transpose(2, 3))),
         ("pixel stride", lambda: wrw(dy, act(2, 20, 5, 6)[:, :16])),
+        ("16-byte aligned", lambda: wrw(dy, _off_grid(x))),
         ("multiple of 8", lambda: wrw(dy, act(2, 12, 5, 6))),
         ("multiple of 8", lambda: wrw(act(2, 20, 10, 12), x)),
         ("gives a gradient of", lambda: wrw(dy[:1], x)),

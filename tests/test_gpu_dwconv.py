@@ -27,8 +27,8 @@ import torch
 
 from dwconv_cases import (SMALL, channels, dw_ref, exact_inputs, out_size,
                           real_inputs, seen_weight)
-from test_gpu_bn import (BF16, FP32, _DEV, _bits_equal, _ext, _half_ulp, _vec,
-                         gpu, requires_gpu)
+from test_gpu_bn import (BF16, FP32, _DEV, _bits_equal, _ext, _half_ulp,
+                         _off_grid, _vec, gpu, requires_gpu)
 
 CL = torch.channels_last
 
@@ -301,6 +301,10 @@ def test_bindings_reject_layout():
     with pytest.raises(RuntimeError, match="channels_last"):
         ext.dwconv3x3_dgrad(torch.ones((), device=_DEV, dtype=BF16)
                             .expand_as(dy), w, 1, 5, 6)
+    with pytest.raises(RuntimeError, match="16-byte aligned"):
+        ext.dwconv3x3_fwd(_off_grid(x), w, 1)
+    with pytest.raises(RuntimeError, match="16-byte aligned"):
+        ext.dwconv3x3_wrw(_off_grid(dy), x, 1)
 
 
 @gpu

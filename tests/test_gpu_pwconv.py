@@ -18,7 +18,8 @@ import torch
 from pwconv_cases import (BF16, CL, FP32, SHAPES, exact_inputs, exact_premise,
                           pw_ref, real_inputs)
 from tensorflowonspark_amd.ops.modules import PointwiseConv
-from test_gpu_bn import _DEV, _bits_equal, _ext, _half_ulp, gpu, requires_gpu
+from test_gpu_bn import (_DEV, _bits_equal, _ext, _half_ulp, _off_grid, gpu,
+                         requires_gpu)
 
 DIRECTIONS = ("fwd", "dgrad")
 _ENTRIES = ("pwconv_fwd", "pwconv_dgrad", "conv_wrw2")
@@ -138,6 +139,7 @@ def test_bindings_reject_bad_arguments():
         ("must be bf16", lambda: dgrad(dy.float(), w)),
         ("channels_last", lambda: fwd(x.contiguous(), w)),
         ("channels_last", lambda: dgrad(dy[:1, :1, :1, :1].expand_as(dy), w)),
+        ("16-byte aligned", lambda: fwd(_off_grid(x), w)),
         ("4-D", lambda: fwd(x[0], w)),
         (r"\[Cout,Cin,1,1\]", lambda: fwd(x, w.half())),
         (r"\[Cout,Cin,1,1\]", lambda: fwd(x, w[:, :, 0, 0])),

@@ -5,7 +5,7 @@ Tiers and their cases: docs/components.md, "Bilinear upsampling coverage"."""
 import pytest
 import torch
 
-from test_gpu_bn import _DEV, _bits_equal, _ext, gpu, requires_gpu
+from test_gpu_bn import _DEV, _bits_equal, _ext, _off_grid, gpu, requires_gpu
 from upsample_cases import (BF16, CASES, CL, FP32, bounds, case_id, inputs,
                             ub_ref)
 
@@ -110,6 +110,7 @@ def test_bindings_reject_bad_arguments():
         ("bf16 or fp32", lambda: fwd(x.half(), 8, 10, False)),
         ("channels_last", lambda: fwd(x.contiguous(), 8, 10, False)),
         ("channels_last", lambda: bwd(x[:1, :1, :1, :1].expand_as(x), 2, 2, False)),
+        ("16-byte aligned", lambda: fwd(_off_grid(x), 8, 10, False)),
         ("upscale only", lambda: fwd(x, 3, 10, False)),
         ("upscale only", lambda: bwd(x, 5, 5, False)),
         (r"sizes must be in \[1,", lambda: fwd(x, 8, 2 ** 31, False)),
